@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """bench.py -- gaps/s and filled-bases/s of the MI355X gap-fill engine on the synthetic 10^5-gap set of
-BASELINE.json (SURVEY.md §8d recipe), with the FP64 roofline of the dominant kernel and the CPU baseline.
+BASELINE.json (SURVEY.md §8d recipe), with the FP64 roofline of the dominant kernel (and, with --full, the CPU baseline).
 
   python bench.py --gpus N --steps K --warmup W
   (N > 1 without a launcher: bench.py starts its own N ranks -- `python -m torch.distributed.run --nnodes=1
@@ -17,14 +17,18 @@ sample of that distribution, resident in HBM (`full_set_seconds_est` extrapolate
 Multi-GPU: every rank generates the same global sample (same seed), the product's partitioner
 (figbird_amd.dist.partition_lpt on estimate_cost: the role of FillGaps.cpp:456-649) deals it into N shards, each rank
 fills its shard through the C ABI, and one all-gather of packed byte buffers per step reassembles the results.
-`--scaling strong` (default): ONE fixed seeded set of `--total-gaps` gaps (default 8 x `--gaps-per-gpu` = 4096) whatever N is
--- BASELINE's metric is one set filled at 1/2/4/8 GPUs, so N = 1 fills all 4096 gaps per step and N = 8 fills 512 per rank;
+`--scaling strong` (default): ONE fixed seeded set of `--total-gaps` gaps (default 8 x `--gaps-per-gpu` = 256) whatever N is
+-- BASELINE's metric is one set filled at 1/2/4/8 GPUs, so N = 1 fills all 256 gaps per step and N = 8 fills 32 per rank;
 `--scaling weak`: the sample is `--gaps-per-gpu` x N gaps.
 
-Wall budget: the whole run (imports, generation, warm-up and timed steps, then the CPU baseline, the partial pass and the
-per-bracket probes) is kept inside `--budget-s` seconds.  The first fill is timed; warm-up and step counts are then clamped
-to what fits (with a reserve for the extras that follow the timed loop) and the line reports the counts actually run
-(`steps`, `warmup`) beside `requested_steps` / `requested_warmup`.
+A plain run sets up, runs exactly `--warmup` warm-up fills and `--steps` timed fills, and prints the line: `value` (gaps/s),
+`ms_per_step`, and the roofline of the timed steps' kernels.  `--dump-outputs DIR` then writes what the last timed step
+computed (see dump_outputs).
+
+`--full` adds the extras that follow the timed loop: the CPU baseline, the partial-mode pass and the per-bracket probes.
+Such a run is kept inside `--budget-s` seconds: the first fill is timed, warm-up and step counts are then clamped to what
+fits (with a reserve for the extras) and the line reports the counts actually run (`steps`, `warmup`) beside
+`requested_steps` / `requested_warmup`.
 One JSON line on stdout (rank 0), also when the budget runs out or the process receives SIGTERM."""
 from __future__ import annotations
 
@@ -126,20 +130,29 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras after the timed loop (CPU baseline, partial-mode pass, per-bracket probes) inside --budget-s")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64 / float32)")
     ap.add_argument("--budget-s", type=float, default=float(os.environ.get("FIGBENCH_BUDGET_S", "540")),
-                    help="wall budget of the whole run; warm-up/steps are clamped to fit")
-    ap.add_argument("--gaps-per-gpu", type=int, default=512)
+                    help="with --full: wall budget of the whole run; warm-up/steps are clamped to fit")
+    # a step is one fill of the whole set, and --steps / --warmup are run exactly: the default set (8 x 32 = 256 gaps of the
+    # recipe, ~11 s per step on one MI355X) lets a run of 20 + 5 steps finish in under 5 minutes; the 4 096-gap set of earlier
+    # rounds (~150 s per step, i.e. over an hour for 20 + 5) is --total-gaps 4096
+    ap.add_argument("--gaps-per-gpu", type=int, default=32)
     ap.add_argument("--reads-per-gap", type=float, default=1000.0)
     ap.add_argument("--mix", default="gage", choices=["gage", "loguniform"])
     ap.add_argument("--mode", default="unmapped", choices=["unmapped", "partial"])
     ap.add_argument("--seed", type=int, default=20260101)
-    ap.add_argument("--cpu-baseline", type=int, default=1)
-    ap.add_argument("--partial-pass", type=int, default=1, help="also report the partial-mode pass (untimed extra)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: measure the CPU baseline")
+    ap.add_argument("--partial-pass", type=int, default=1, help="with --full: also report the partial-mode pass (untimed extra)")
     ap.add_argument("--cpu-sample-gaps", type=int, default=0, help="0 = five gaps per host core from the >400-bp bracket")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"], help="strong: one fixed set of --total-gaps for every N; weak: gaps-per-gpu x N gaps")
     ap.add_argument("--total-gaps", type=int, default=0, help="size of the fixed set of --scaling strong (0 = 8 x gaps-per-gpu)")
-    ap.add_argument("--bracket-probes", type=int, default=1, help="measure the cheap per-bracket probes inside this run (N=1 only)")
+    ap.add_argument("--bracket-probes", type=int, default=1, help="with --full: measure the cheap per-bracket probes inside this run (N=1 only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # No launcher around us: start the N ranks ourselves.  Decided before torch / HIP are touched in this process, which
         # stays a plain parent (it never initialises the GPU, the ranks are fresh child processes, nothing is exec'ed).
@@ -217,9 +230,11 @@ def main():
         if world > 1:
             fl, gt, ss = fdist.all_gather_packed(my_ids, res, n_global, device=dev)
             filled = ss.filled_bases()
+            outs = (fl, gt, ss.off, ss.raw)
         else:
             filled = res.filled_bases
-        return res, filled, eng.stats()
+            outs = (res.filled_len, res.gaptofill, res.str_off, res.raw)
+        return res, filled, eng.stats(), outs
 
     def barrier():
         if world > 1:
@@ -246,31 +261,34 @@ def main():
                    "sharding": f"{n_global} gaps dealt LPT on estimated cost over {world} rank(s), no data-path collective, 1 all-gather of packed results per step"},
     })
 
-    # ---- first fill: timed on its own, counts as warm-up; everything after it is clamped to the budget
+    # ---- first fill: timed on its own, counts as warm-up; with --full everything after it is clamped to the budget
     # (--warmup 0: no first fill and no clamping -- exactly --steps fills, for the profiler passes of tools/profile_bench.sh)
     barrier()
     if args.warmup > 0:
         t0 = time.perf_counter()
-        res, filled, st = one_step()
+        res, filled, st, _ = one_step()
         barrier()
         t_first = allmax(time.perf_counter() - t0)
         warm_done = 1
-        log(f"first fill {t_first:.1f} s ({st['kernel_ms'] / 1e3:.1f} s of kernels), {left():.0f} s of budget left")
+        log(f"first fill {t_first:.1f} s ({st['kernel_ms'] / 1e3:.1f} s of kernels)" + (f", {left():.0f} s of budget left" if args.full else ""))
     else:
         t_first, warm_done = 0.0, 0
 
-    # ---- clamp warm-up and steps to what is left (10 s reserve for teardown); the timed steps come before the extras
-    # N = 1 keeps a reserve for the extras that follow the timed loop (CPU baseline ~60 s, partial pass ~10 s, bracket probes ~35 s)
-    extras_reserve = 110.0 if (world == 1 and (args.cpu_baseline or args.partial_pass or args.bracket_probes)) else 0.0
-    left_min = -allmax(-left())                       # the rank with the least budget left decides
-    fit = int(max(0.0, left_min - 10.0 - extras_reserve) / max(t_first, 1e-3)) if warm_done else args.steps
-    steps = max(1, min(args.steps, fit))
-    warm_more = max(0, min(args.warmup - warm_done, fit - steps))
-    if world > 1:
-        import torch.distributed as dist
-        t = torch.tensor([steps, warm_more], dtype=torch.int64, device=dev)
-        dist.broadcast(t, src=0)
-        steps, warm_more = int(t[0]), int(t[1])
+    if args.full:
+        # ---- clamp warm-up and steps to what is left (10 s reserve for teardown); the timed steps come before the extras
+        # N = 1 keeps a reserve for the extras that follow the timed loop (CPU baseline ~60 s, partial pass ~10 s, bracket probes ~35 s)
+        extras_reserve = 110.0 if (world == 1 and (args.cpu_baseline or args.partial_pass or args.bracket_probes)) else 0.0
+        left_min = -allmax(-left())                       # the rank with the least budget left decides
+        fit = int(max(0.0, left_min - 10.0 - extras_reserve) / max(t_first, 1e-3)) if warm_done else args.steps
+        steps = max(1, min(args.steps, fit))
+        warm_more = max(0, min(args.warmup - warm_done, fit - steps))
+        if world > 1:
+            import torch.distributed as dist
+            t = torch.tensor([steps, warm_more], dtype=torch.int64, device=dev)
+            dist.broadcast(t, src=0)
+            steps, warm_more = int(t[0]), int(t[1])
+    else:
+        steps, warm_more = args.steps, args.warmup - warm_done
     log(f"running {warm_more} more warm-up + {steps} timed steps (requested {args.warmup}/{args.steps})")
     for _ in range(warm_more):
         one_step()
@@ -280,11 +298,14 @@ def main():
     flops = 0.0
     place_calls = 0
     for i in range(steps):
-        res, filled, st = one_step()
+        res, filled, st, outs = one_step()
         kernel_ms += st["kernel_ms"]; flops += st["alg_flops"]; place_calls += st["place_calls"]
         log(f"step {i + 1}/{steps}: kernels {st['kernel_ms'] / 1e3:.2f} s")
     barrier()
     elapsed = allmax(time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:
+        OUT["dump_outputs"] = dump_outputs(args.dump_outputs, *outs, n_global, args.seed)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     per_rank_kernel_ms = [kernel_ms / steps]
     if world > 1:
         import torch.distributed as dist
@@ -332,9 +353,9 @@ def main():
         OUT["roofline"]["mle_fraction_executed"] = mle_done
         OUT["roofline"]["executed_frac"] = OUT["roofline"]["frac"] * (1.0 - mle_share * (1.0 - mle_done))
         OUT["roofline"]["discarded_speculation_frac"] = max(0.0, 1.0 - st["alg_flops"] / st["spec_flops"])
-    # ---- CPU baseline, the other mode's pass and the per-bracket probes (rank 0, N=1 only): after the timed loop, inside what is left of the budget
+    # ---- --full: CPU baseline, the other mode's pass and the per-bracket probes (rank 0, N=1 only): after the timed loop, inside what is left of the budget
     extras_s = 0.0
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline:
         if left() > 45:
             t = time.perf_counter()
             try:
@@ -345,7 +366,7 @@ def main():
             log(f"cpu_baseline done in {time.perf_counter() - t:.1f} s")
         else:
             OUT["cpu_baseline"] = {"value": None, "unit": "gaps/s", "cores": 0, "kind": "reference", "sample": "skipped: wall budget too short"}
-    if rank == 0 and world == 1 and args.mode == "unmapped" and args.partial_pass and left() > 25:
+    if args.full and rank == 0 and world == 1 and args.mode == "unmapped" and args.partial_pass and left() > 25:
         t = time.perf_counter()
         try:
             OUT["partial_pass"] = partial_pass(args, local, work)
@@ -353,7 +374,7 @@ def main():
             OUT["partial_pass"] = {"value": None, "unit": "gaps/s", "note": f"failed: {e!r}"}
         extras_s += time.perf_counter() - t
 
-    if rank == 0 and world == 1 and args.mode == "unmapped" and args.bracket_probes and left() > 30:
+    if args.full and rank == 0 and world == 1 and args.mode == "unmapped" and args.bracket_probes and left() > 30:
         t = time.perf_counter()
         try:
             OUT["per_bracket"] = bracket_probes(args, eng, batch, spec, min(45.0, left() - 12))
@@ -392,11 +413,39 @@ def main():
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
-    if rank == 0 and args.mode == "unmapped":
+    if args.full and rank == 0 and args.mode == "unmapped":
         OUT.setdefault("per_bracket", {})["from_file"] = read_brackets()
     OUT["fills_run"] = warm_done + warm_more + steps        # fills of the main batch (what a profiler around this command sees)
     OUT["wall_s_total"] = time.perf_counter() - T_PROC0
     emit()
+
+
+DUMP_LIMIT_BYTES = (64 << 20) - 4096          # 64 MB in all, the .npy headers included
+
+
+def dump_outputs(dirname, filled_len, gaptofill, str_off, raw, n_gaps, seed):
+    """What a caller of the timed path receives from the last timed step, in global gap order, as DIR/<name>.npy:
+    gap_ids, filled_len, gaptofill and str_off in float64; gap_bases in float32, the byte values of the filled gap strings
+    back to back (gap_ids[i]'s string is gap_bases[str_off[i]:str_off[i + 1]]).  Every gap while the files stay within
+    64 MB; beyond that a fixed sample of the gaps, drawn with `seed`."""
+    off = np.asarray(str_off[:n_gaps + 1], dtype=np.int64)
+    lens = np.diff(off)
+    ids = np.arange(n_gaps)
+    if 8 * (4 * n_gaps + 1) + 4 * int(lens.sum()) > DUMP_LIMIT_BYTES:
+        perm = np.random.default_rng(seed).permutation(n_gaps)
+        fits = np.cumsum(8 * 4 + 4 * lens[perm]) <= DUMP_LIMIT_BYTES - 8
+        ids = np.sort(perm[fits])
+    raw = np.asarray(raw, dtype=np.uint8)
+    bases = np.concatenate([raw[off[g]:off[g + 1]] for g in ids]) if len(ids) else np.zeros(0, dtype=np.uint8)
+    sub_off = np.zeros(len(ids) + 1, dtype=np.int64)
+    sub_off[1:] = np.cumsum(lens[ids])
+    arrays = {"gap_ids": ids.astype(np.float64), "filled_len": np.asarray(filled_len[:n_gaps])[ids].astype(np.float64),
+              "gaptofill": np.asarray(gaptofill[:n_gaps])[ids].astype(np.float64), "str_off": sub_off.astype(np.float64),
+              "gap_bases": bases.astype(np.float32)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "gaps": int(len(ids)), "of_gaps": int(n_gaps), "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def bracket_probes(args, eng, main_batch, spec, budget_s):

@@ -1,5 +1,6 @@
 """The C-ABI shared library and the host-side mirror (no GPU compute)."""
 import ctypes
+import json
 import os
 import re
 
@@ -150,29 +151,24 @@ def test_model_build_threads_agree(tmp_path, monkeypatch):
     assert a.ins.max() > a.ins.min()            # the indel reads really fed inPosDist
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(util.REF_FIGBIRD), "FillGaps.out")) or not os.path.exists("/root/reference/Figbird.cpp"),
-                    reason="needs oracle/_ref (the reference compiled in place) and the reference checkout")
 @pytest.mark.parametrize("lens,threads", [([20, 500, 25, 600, 18, 33, 700], 5), ([500, 20, 600, 700, 30, 800, 900, 450, 25, 1000, 40, 1100], 3)])
 def test_gap_deal_matches_live_reference(lens, threads, tmp_path):
     """FillGaps.cpp:456-649 deals the gaps to $num_threads worker processes (short gaps in turn, long ones by remaining
     capacity); `figfill` reproduces it (fig_host.cpp: thread_allocation) for gaploads.txt, the order of draw.txt and the
-    process-level overlap_threshold, and so does the oracle.  Read-less gaps keep this quick: the reference compiles
-    Figbird.cpp once per process.  (The committed `threads3` fixture pins the short-gap branch with reads.)"""
+    process-level overlap_threshold, and so does the oracle.  Read-less gaps keep this quick.  The reference's FillGaps.out
+    output on these cases is recorded in tests/golden/gap_deal.json (tools/make_deal_golden.py).  (The committed `threads3`
+    fixture pins the short-gap branch with reads.)"""
     from figbird_amd import synth
-    specs, pos = [], 300
-    for n in lens:
-        specs.append((pos, n)); pos += n + 400
-    case = synth.make_case("deal", 5, "unmapped", specs, contig_len=pos + 400, coverage=0.0, n_model_pairs=300)
-    outs = {}
-    for tag, exe in (("ref", [os.path.join(os.path.dirname(util.REF_FIGBIRD), "FillGaps.out")]), ("host", [util.EMU]), ("oracle", [util.ORACLE, "fillgaps"])):
+    from tools.make_deal_golden import FILES, deal_case
+    with open(os.path.join(util.GOLDEN, "gap_deal.json")) as f:
+        ref = next(g for g in json.load(f).values() if g["lens"] == lens and g["threads"] == threads)["files"]
+    case = deal_case(lens)
+    for tag, exe in (("host", [util.EMU]), ("oracle", [util.ORACLE, "fillgaps"])):
         p = synth.write_case(case, str(tmp_path / tag))
         cwd = tmp_path / ("cwd_" + tag); cwd.mkdir()
-        os.symlink("/root/reference/Figbird.cpp", str(cwd / "Figbird.cpp"))         # FillGaps.out shells out to g++ Figbird.cpp
         r = util.run(exe + synth.fillgaps_argv(case, p, n_threads=threads), str(cwd), timeout=600)
         assert r.returncode == 0, r.stderr
-        outs[tag] = {fn: util.read(p["tmp"] + fn) for fn in ("gaploads.txt", "draw.txt", "gapout.txt", "filledContigs.fa")}
-    assert outs["host"] == outs["ref"]
-    assert outs["oracle"] == outs["ref"]
+        assert {fn: util.read(p["tmp"] + fn) for fn in FILES} == ref, tag
 
 
 def _run_handle(root):

@@ -11,7 +11,7 @@ import pytest
 import util
 from tools.compare_prep import mask_gap_file
 
-HAVE_REF = os.path.exists(os.path.join(util.ROOT, "oracle", "_ref", "Preprocess.out")) and os.path.exists("/root/reference/reference.py")
+HAVE_REF = all(os.path.exists(os.path.join(util.ROOT, "oracle", "_ref", f)) for f in ("Preprocess.out", "Reduce_SCF.out"))   # what tools/compare_prep runs
 
 
 def _tool(args, cwd):
@@ -128,6 +128,35 @@ def test_preprocess_fast_and_legacy_forms_agree(seed, threads, tmp_path):
 def test_preprocess_live_against_reference(seed, tmp_path):
     from tools.compare_prep import run_one
     assert run_one(seed, str(tmp_path), verbose=False, end_gap=(seed % 3 == 0), n_contigs=1 + seed % 3, n_frag=900, n_jump=900)
+
+
+def test_driver_patch_touches_only_the_stage_command_lines():
+    """The part of the check below that needs no reference checkout: integration/RunFigbird.patch inserts the FIGBIRD_AMD
+    guard after line 2 and replaces, one line for one line, exactly the 14 stage command lines -- each a `g++ X.cpp && ./a.out`
+    or `python reference.py` line of the reference script -- by the same arguments given to figfill / figtool."""
+    import re
+    hunks, cur = [], None
+    for ln in open(os.path.join(util.ROOT, "integration", "RunFigbird.patch")).read().split("\n"):
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", ln)
+        if m:
+            cur = {"old": int(m.group(1)), "n_old": int(m.group(2) or 1), "minus": [], "plus": []}
+            hunks.append(cur)
+        elif cur is not None and ln.startswith("-"):
+            cur["minus"].append(ln[1:])
+        elif cur is not None and ln.startswith("+"):
+            cur["plus"].append(ln[1:])
+    guard, edits = hunks[0], hunks[1:]
+    assert (guard["old"], guard["n_old"], guard["minus"], len(guard["plus"])) == (2, 0, [], 2) and "FIGBIRD_AMD" in guard["plus"][1]
+    assert [h["old"] for h in edits] == [254, 256, 266, 285, 320, 338, 352, 433, 435, 451, 472, 480, 777, 809]
+    for h in edits:
+        assert len(h["minus"]) == 1 and len(h["plus"]) == 1, h
+        old, new = h["minus"][0], h["plus"][0]
+        assert re.search(r"g\+\+ (-std=c\+\+11 -pthread )?\w+\.cpp && \./a\.out|python reference\.py", old), old
+        assert '"$FIGBIRD_AMD/bin/fig' in new and "g++" not in new and "reference.py" not in new, new
+        args = lambda s: re.split(r"\./a\.out|reference\.py|/bin/fig\w+\"(?: [\w-]+)?", s, maxsplit=1)[1].strip()
+        assert args(old) == args(new), (old, new)
+    plus = "\n".join(h["plus"][0] for h in edits)
+    assert plus.count('"$FIGBIRD_AMD/bin/figfill"') == 2 and plus.count('"$FIGBIRD_AMD/bin/figtool"') == 12
 
 
 @pytest.mark.skipif(not os.path.exists("/root/reference/RunFigbird.sh"), reason="needs the reference's driver script (this container only)")

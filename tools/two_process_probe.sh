@@ -1,5 +1,5 @@
 set -e
-A="--scaling weak --steps 2 --warmup 1 --cpu-baseline 0 --partial-pass 0 --bracket-probes 0"
+A="--scaling weak --gaps-per-gpu 512 --steps 2 --warmup 1 --cpu-baseline 0 --partial-pass 0 --bracket-probes 0"
 python3 bench.py $A > gpurun_out/tp_single.json 2> gpurun_out/tp_single.err
 python3 bench.py $A > gpurun_out/tp_a.json 2> gpurun_out/tp_a.err &
 P1=$!
