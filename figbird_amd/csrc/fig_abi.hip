@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,10 +19,9 @@
 #include "../../include/figbird_hip.h"
 #include "fig_engine.h"
 #include "fig_pack.h"
+#include "fig_abi_host.h"
 
 // ------------------------------------------------------------------------------------- kernel
-// LDS carve-up (doubles first so everything stays 8-byte aligned), LDS_TAB only:
-//   PQ[4][ncolE] (16 B each)  Q4[ncolE]  wbuf[nteams][Wcap]  | FigState  gs[capGl]  rb[FIG_MAX_READLEN+8]
 #ifdef FIG_PROF
 #define FIG_PROF_BEGIN() const unsigned long long _k0 = __builtin_readcyclecounter()
 #define FIG_PROF_FLUSH() do { if (E.lane == 0) { atomicAdd(&B.counters[30], E.wait_cycles); atomicAdd(&B.counters[31], (unsigned long long)__builtin_readcyclecounter() - _k0); \
@@ -33,63 +31,56 @@
 #define FIG_PROF_BEGIN() ((void)0)
 #define FIG_PROF_FLUSH() ((void)0)
 #endif
-// MLE-pass accounting (raw totals incl. discarded speculation; only their ratio is reported): [3] credited, [4] executed
-#define FIG_FLUSH_MLE() do { if (E.mle_alg) atomicAdd(&B.counters[3], E.mle_alg); if (E.lane == 0 && E.mle_exec) atomicAdd(&B.counters[4], E.mle_exec); } while (0)
-struct FigKernArgs { int capG, capGl, ncolE, Wcap, nteams, q_begin, q_end, qsel, tiles, tile_step, tile_cols, tiled_max, sh_on; };
 
+// What depends on the launch (thread identity, the workgroup's slab); the LDS / slab layout is fig_eng_carve (fig_engine.h).
 FIG_D void fig_eng_init(FigEng &E, const FigDevModel &M, const FigDevBatch &B, const FigKernArgs &A, bool lds_tab, FigScr &work) {
     E.tid = threadIdx.x; E.nt = blockDim.x;
     E.lane = threadIdx.x & 63; E.wave = threadIdx.x >> 6; E.nw = (blockDim.x + 63) >> 6; E.wsz = 64;
     E.M = &M; E.B = &B;
-    E.capG = A.capG; E.flops = 0; E.mle_alg = 0; E.mle_exec = 0; E.wait_cycles = 0;
+    E.flops = 0; E.mle_alg = 0; E.mle_exec = 0; E.wait_cycles = 0;
     for (int i = 0; i < 40; i++) E.prof[i] = 0;
-    E.ncolE = A.ncolE; E.xoff = M.L - 1; E.Wcap = A.Wcap; E.nteams = A.nteams; E.sh_on = A.sh_on;
     unsigned char *slab = B.scratch + (long long)blockIdx.x * B.scratch_stride;
     fig_scratch_layout(slab, B.capG, B.capR, B.capP, B.capC, B.capW, B.capE, &work);
     E.scr = work;
-    long long off = 0;
-    E.pq_lds = lds_tab; E.w_lds = lds_tab;
-    E.tiles = A.tiles; E.tile_step = A.tile_step; E.tile_cols = A.tile_cols;
-    if (lds_tab && A.tiles > 0) {
-        // LDS-tiled class: LDS = {table tile [4][tile_cols] + Q4 tile, weight rows}; the full table, and the buffers of the
-        // MLE pass (which runs its HBM-table form), stay in the scratch slab
-        E.pq_lds = 0;
-        E.off_pq = 0; E.off_q4 = 8 * A.tile_cols; E.off_w = 9 * A.tile_cols;
-        off = 9LL * A.tile_cols + (long long)A.nteams * A.Wcap;
-        { const long long mle = FIG_TILED_MLE_DOUBLES(A.ncolE, (int)E.nw); if (mle > off && mle <= A.tiled_max) off = mle; }   // as fig_pack sized it
-        E.pq = E.scr.pqg; E.q4 = E.scr.q4g; E.wbuf = E.scr.wg;
-    } else if (lds_tab) {
-        E.off_pq = 0; E.off_q4 = 8 * A.ncolE; E.off_w = 9 * A.ncolE;
-        off = 9LL * A.ncolE + (long long)A.nteams * A.Wcap;
-        E.pq = (FigPQ *)(fig_lds + E.off_pq); E.q4 = fig_lds + E.off_q4; E.wbuf = fig_lds + E.off_w;
-    } else {
-        E.off_pq = E.off_q4 = E.off_w = 0;
-        E.pq = E.scr.pqg; E.q4 = E.scr.q4g; E.wbuf = E.scr.wg;
-    }
-    E.S = (FigState *)(fig_lds + off); E.lds_tw = (int)off;
-    unsigned char *bp = (unsigned char *)(E.S + 1);
-    E.gs = bp; bp += ((A.capGl + 7) & ~7);
-    E.rb = bp; bp += ((FIG_MAX_READLEN + 8 + 15) & ~15);
-    E.plb = (uint32_t *)bp; E.off_plb = (int)((double *)bp - fig_lds);
-    E.kt_fwd = M.ome; E.kt_rev = M.ome + 2 * M.L; E.mt_fwd = M.ome + 4 * M.L; E.mt_rev = M.ome + 6 * M.L;
+    fig_eng_carve(E, M, A, lds_tab);
 }
 
 FIG_D void fig_persist_of(const FigDevBatch &B, const FigDevGap &g, FigPersist &P) {
     fig_persist_layout(B.persist + g.persistOff, g.capGg, g.nU, g.nP, g.rangeCap, g.nslots, sizeof(FigState), &P);
 }
 
+// Prologue of the five persistent kernels.  Every persistent launch pops from one of its lane's two queue heads and zeroes the
+// other for its successor.
+FIG_D void fig_kernel_begin(FigEng &E, const FigDevModel &M, const FigDevBatch &B, const FigKernArgs &A, bool lds_tab, FigScr &work) {
+    fig_eng_init(E, M, B, A, lds_tab, work);
+    if (blockIdx.x == 0 && threadIdx.x == 0) B.queue_head[A.qsel ^ 1] = 0;      // the next launch of this lane pops from the other head
+}
+
+// Next index of the launch's work queue, the same in every lane of the workgroup.
+FIG_D int fig_queue_pop(FigEng &E, const FigDevBatch &B, const FigKernArgs &A) {
+    if (E.tid == 0) E.S->bc_i = atomicAdd(B.queue_head + A.qsel, 1);
+    __syncthreads();
+    const int qi = E.S->bc_i;
+    __syncthreads();
+    return qi;
+}
+
+// Epilogue: algorithmic flops, and the MLE-pass accounting (raw totals incl. discarded speculation; only their ratio is
+// reported): [3] credited, [4] executed
+FIG_D void fig_kernel_flush(const FigEng &E, const FigDevBatch &B) {
+    if (E.flops) atomicAdd(&B.counters[1], E.flops);
+    if (E.mle_alg) atomicAdd(&B.counters[3], E.mle_alg);
+    if (E.lane == 0 && E.mle_exec) atomicAdd(&B.counters[4], E.mle_exec);
+}
+
 // ---- sequential mode: whole gaps, one workgroup each (FIG_SCHED=seq)
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_fill_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A) {
     FigEng E; FigScr work;
-    fig_eng_init(E, M, B, A, LDS_TAB, work);
-    if (blockIdx.x == 0 && threadIdx.x == 0) B.queue_head[A.qsel ^ 1] = 0;      // the next launch of this lane pops from the other head
+    fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     FIG_PROF_BEGIN();
     while (true) {
-        if (E.tid == 0) E.S->bc_i = atomicAdd(B.queue_head + A.qsel, 1);
-        __syncthreads();
-        int qi = A.q_begin + E.S->bc_i;
-        __syncthreads();
+        const int qi = A.q_begin + fig_queue_pop(E, B, A);
         if (qi >= A.q_end) break;
         E.g = &B.gaps[B.order[qi]];
         FigPersist P; fig_persist_of(B, *E.g, P);
@@ -97,21 +88,16 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_fill_kernel(FigDe
         fig_fill_gap<LDS_TAB>(E);
     }
     FIG_PROF_FLUSH();
-    if (E.flops) atomicAdd(&B.counters[1], E.flops);
-    FIG_FLUSH_MLE();
+    fig_kernel_flush(E, B);
 }
 
 // ---- candidate-parallel mode, kernel 1: setup + analyzeGap + checkGapReads per gap; skipped gaps finish here
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_begin_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A) {
     FigEng E; FigScr work;
-    fig_eng_init(E, M, B, A, LDS_TAB, work);
-    if (blockIdx.x == 0 && threadIdx.x == 0) B.queue_head[A.qsel ^ 1] = 0;      // the next launch of this lane pops from the other head
+    fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     while (true) {
-        if (E.tid == 0) E.S->bc_i = atomicAdd(B.queue_head + A.qsel, 1);
-        __syncthreads();
-        int qi = A.q_begin + E.S->bc_i;
-        __syncthreads();
+        const int qi = A.q_begin + fig_queue_pop(E, B, A);
         if (qi >= A.q_end) break;
         int gi = B.order[qi];
         E.g = &B.gaps[gi];
@@ -128,21 +114,16 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_begin_kernel(FigD
         }
         __syncthreads();
     }
-    if (E.flops) atomicAdd(&B.counters[1], E.flops);
-    FIG_FLUSH_MLE();
+    fig_kernel_flush(E, B);
 }
 
 // ---- pre-pass (partial mode): per gap, does its candidate loop get to Figbird.cpp:6317?  -> gapctl[gi*4+3]
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_probe_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A) {
     FigEng E; FigScr work;
-    fig_eng_init(E, M, B, A, LDS_TAB, work);
-    if (blockIdx.x == 0 && threadIdx.x == 0) B.queue_head[A.qsel ^ 1] = 0;      // the next launch of this lane pops from the other head
+    fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     while (true) {
-        if (E.tid == 0) E.S->bc_i = atomicAdd(B.queue_head + A.qsel, 1);
-        __syncthreads();
-        int qi = A.q_begin + E.S->bc_i;
-        __syncthreads();
+        const int qi = A.q_begin + fig_queue_pop(E, B, A);
         if (qi >= A.q_end) break;
         int gi = B.order[qi];
         E.g = &B.gaps[gi];
@@ -158,14 +139,10 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_probe_kernel(FigD
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_eval_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A, const int4 *items, int n_items) {
     FigEng E; FigScr work;
-    fig_eng_init(E, M, B, A, LDS_TAB, work);
-    if (blockIdx.x == 0 && threadIdx.x == 0) B.queue_head[A.qsel ^ 1] = 0;      // the next launch of this lane pops from the other head
+    fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     FIG_PROF_BEGIN();
     while (true) {
-        if (E.tid == 0) E.S->bc_i = atomicAdd(B.queue_head + A.qsel, 1);
-        __syncthreads();
-        int qi = E.S->bc_i;
-        __syncthreads();
+        const int qi = fig_queue_pop(E, B, A);
         if (qi >= n_items) break;
         int4 it = items[qi];
         E.g = &B.gaps[it.x];
@@ -174,11 +151,12 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_eval_kernel(FigDe
         __syncthreads();
     }
     FIG_PROF_FLUSH();
-    if (E.flops) atomicAdd(&B.counters[1], E.flops);
-    FIG_FLUSH_MLE();
+    fig_kernel_flush(E, B);
 }
 
 // ---- kernel 3: replay the bookkeeping of the speculated candidates in order; entries = {gap, n slots, -, -}
+// One wave, no class: it touches FigState alone, and its launch asks for no more LDS than that.  fig_eng_carve would place gs /
+// rb / plb behind FigState, outside that request, so this kernel keeps them null (a stray use faults instead of corrupting).
 __global__ void __launch_bounds__(64) fig_replay_kernel(FigDevModel M, FigDevBatch B, const int4 *entries, int n) {
     if ((int)blockIdx.x >= n) return;
     FigEng E; FigScr work;
@@ -199,13 +177,9 @@ __global__ void __launch_bounds__(64) fig_replay_kernel(FigDevModel M, FigDevBat
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_end_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A, const int *list, int n) {
     FigEng E; FigScr work;
-    fig_eng_init(E, M, B, A, LDS_TAB, work);
-    if (blockIdx.x == 0 && threadIdx.x == 0) B.queue_head[A.qsel ^ 1] = 0;      // the next launch of this lane pops from the other head
+    fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     while (true) {
-        if (E.tid == 0) E.S->bc_i = atomicAdd(B.queue_head + A.qsel, 1);
-        __syncthreads();
-        int qi = E.S->bc_i;
-        __syncthreads();
+        const int qi = fig_queue_pop(E, B, A);
         if (qi >= n) break;
         int gi = list[qi];
         E.g = &B.gaps[gi];
@@ -216,8 +190,7 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_end_kernel(FigDev
         if (E.tid == 0) B.gapctl[gi * 4] = 0;
         __syncthreads();
     }
-    if (E.flops) atomicAdd(&B.counters[1], E.flops);
-    FIG_FLUSH_MLE();
+    fig_kernel_flush(E, B);
 }
 
 // ---- upload-time kernel: the operand-select stream of the shared-factor E-step (fig_engine_shared.h).  Entry (read r, chain
@@ -274,7 +247,6 @@ struct fig_ctx {
     int last_hip = 0;
     bool have_model = false;
     FigDevModel dm;
-    std::vector<double> h_e, h_ome, h_m3, h_insd, h_qtab;
     DevBuf d_model_tabs;
     fig_model hm;
     // resident batch
@@ -321,18 +293,7 @@ static int dev_upload(fig_ctx *ctx, const std::vector<T> &v, const T **out) {
 
 extern "C" int fig_version(void) { return FIG_ABI_VERSION; }
 
-extern "C" const char *fig_strerror(int code) {
-    switch (code) {
-        case FIG_OK: return "ok";
-        case FIG_EINVAL: return "invalid argument";
-        case FIG_ENODEV: return "no usable HIP device (libfighip has no CPU path)";
-        case FIG_ENOMEM: return "out of memory";
-        case FIG_EHIP: return "HIP runtime error";
-        case FIG_ENOSPC: return "result string buffer too small";
-        case FIG_EUNSUP: return "input outside the supported envelope";
-        default: return "unknown error";
-    }
-}
+extern "C" const char *fig_strerror(int code) { return fig_strerror_text(code); }
 
 extern "C" int fig_ctx_create(int device_ordinal, fig_ctx **out) {
     if (!out) return FIG_EINVAL;
@@ -358,8 +319,7 @@ extern "C" int fig_ctx_create(int device_ordinal, fig_ctx **out) {
         return FIG_EHIP;
     }
     memset(&ctx->stats, 0, sizeof(ctx->stats));
-    { const char *ev = getenv("FIG_ESTEP"); const char *sc = getenv("FIG_SH_CHUNKS");
-      ctx->sh_on = (ev && !strcmp(ev, "pair")) ? 0 : (sc ? std::max(1, std::min(FIG_SH_SC, atoi(sc))) : FIG_SH_SC); }
+    ctx->sh_on = fig_knobs_from_env(0).sh_on;
     *out = ctx;
     return FIG_OK;
 }
@@ -392,57 +352,18 @@ extern "C" void fig_ctx_destroy(fig_ctx *ctx) {
 }
 
 extern "C" int fig_ctx_set_model(fig_ctx *ctx, const fig_model *m) {
-    if (!ctx || !m || !m->error_pos_dist || !m->in_pos_dist || !m->del_pos_dist || !m->insert_len_dist_smoothed) return FIG_EINVAL;
-    if (m->max_read_length <= 0 || m->max_read_length > FIG_MAX_READLEN) return FIG_EUNSUP;
-    if (m->max_insert_size <= 0) return FIG_EINVAL;
-    if (m->partial_flag && m->unmapped_flag) return FIG_EUNSUP;      // the driver never sets both (RunFigbird.sh:211-216)
-    if (m->insert_threshold_min < 0 || m->insert_threshold_max >= m->max_insert_size + 1) return FIG_EINVAL;
+    if (!ctx) return FIG_EINVAL;
+    if (int rc = fig_model_check(m)) return rc;
     hipSetDevice(ctx->device);
     free_batch(ctx);                  // a resident batch was packed (classes, capacities, candidate ranges) under the previous model
-    int L = m->max_read_length;
     ctx->hm = *m;
-    ctx->h_e.assign(m->error_pos_dist, m->error_pos_dist + L);
-    ctx->h_ome.resize(L); ctx->h_m3.resize(L);
-    for (int k = 0; k < L; k++) {
-        volatile double a = 1 - m->error_pos_dist[k];                 // (1-errorPosDist[k])               Figbird.cpp:3160
-        ctx->h_ome[k] = a;
-        volatile double b = 1 - m->error_pos_dist[k] - m->in_pos_dist[k] - m->del_pos_dist[k];   // Figbird.cpp:3400
-        ctx->h_m3[k] = b;
-    }
-    ctx->h_insd.assign(m->insert_len_dist_smoothed, m->insert_len_dist_smoothed + m->max_insert_size);
-    ctx->h_insd.push_back(0.0);                                       // insertThresholdMax may equal maxInsertSize (:7194)
-    ctx->h_qtab.resize(256);
-    for (int c = 0; c < 256; c++) { int Q = c - 33; ctx->h_qtab[c] = pow(10, -Q / 10.0); }   // qualityFilter, :1791-1792
-    // pair tables for scalar loads: kt = {1-e[k], e[k]}, mt = {1-e-ins-del, e[k]}; the reversed copies serve
-    // reverse-strand reads (readIndex = len-1-j, Figbird.cpp:3569-3576) as rev[(L-len)+j]
-    std::vector<double> pairs((size_t)8 * L);
-    for (int k = 0; k < L; k++) {
-        pairs[2 * k] = ctx->h_ome[k]; pairs[2 * k + 1] = ctx->h_e[k];
-        pairs[2 * L + 2 * k] = ctx->h_ome[L - 1 - k]; pairs[2 * L + 2 * k + 1] = ctx->h_e[L - 1 - k];
-        pairs[4 * L + 2 * k] = ctx->h_m3[k]; pairs[4 * L + 2 * k + 1] = ctx->h_e[k];
-        pairs[6 * L + 2 * k] = ctx->h_m3[L - 1 - k]; pairs[6 * L + 2 * k + 1] = ctx->h_e[L - 1 - k];
-    }
     std::vector<double> all;
-    size_t o_e = 0; all.insert(all.end(), ctx->h_e.begin(), ctx->h_e.end()); while (all.size() % 8) all.push_back(0);
-    size_t o_pairs = all.size(); all.insert(all.end(), pairs.begin(), pairs.end()); while (all.size() % 8) all.push_back(0);
-    size_t o_m3 = all.size(); all.insert(all.end(), ctx->h_m3.begin(), ctx->h_m3.end()); while (all.size() % 8) all.push_back(0);
-    size_t o_insd = all.size(); all.insert(all.end(), ctx->h_insd.begin(), ctx->h_insd.end()); while (all.size() % 8) all.push_back(0);
-    size_t o_q = all.size(); all.insert(all.end(), ctx->h_qtab.begin(), ctx->h_qtab.end());
-    size_t o_ome = all.size(); all.insert(all.end(), ctx->h_ome.begin(), ctx->h_ome.end());
-    size_t nd = all.size();
+    FigModelOffsets o;
+    fig_model_tables(m, all, o, ctx->dm);
     if (ctx->d_model_tabs.p) { hipFree(ctx->d_model_tabs.p); ctx->d_model_tabs.p = nullptr; }
-    if (hipMalloc(&ctx->d_model_tabs.p, nd * sizeof(double)) != hipSuccess) return FIG_ENOMEM;
-    double *d = (double *)ctx->d_model_tabs.p;
-    if (hipMemcpy(d, all.data(), nd * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FIG_EHIP;
-    FigDevModel &dm = ctx->dm;
-    dm.L = L; dm.Tmin = m->insert_threshold_min; dm.Tmax = m->insert_threshold_max; dm.cutoff = m->gap_prob_cutoff;
-    dm.partial_flag = m->partial_flag; dm.unmapped = m->unmapped_flag; dm.script_itr = m->script_itr; dm.D = m->max_distance;
-    dm.read_length = m->read_length; dm.neg_overlap = m->neg_overlap; dm.partial_len = m->partial_len; dm.unm_limit = m->unm_limit;
-    dm.max_insert = m->max_insert_size;
-    for (int i = 0; i < 25; i++) dm.T[i] = m->error_type_probs[i];
-    dm.fmm_up = fig_model_fmm(m);
-    dm.e = d + o_e; dm.ome = d + o_pairs; dm.m3 = d + o_m3; dm.insd = d + o_insd; dm.qtab = d + o_q;
-    dm.ome1 = d + o_ome;
+    if (hipMalloc(&ctx->d_model_tabs.p, all.size() * sizeof(double)) != hipSuccess) return FIG_ENOMEM;
+    if (hipMemcpy(ctx->d_model_tabs.p, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return FIG_EHIP;
+    fig_model_point(ctx->dm, o, (const double *)ctx->d_model_tabs.p);
     ctx->have_model = true;
     return FIG_OK;
 }
@@ -452,7 +373,35 @@ extern "C" int64_t fig_results_capacity(const fig_model *m, const fig_gap_batch 
     return fig_pack_results_capacity(m, b);
 }
 
-static hipError_t launch_any(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, int kind, int blocks, const void *list, int n, int qsel = 0);
+enum FigKind { FIG_K_FILL, FIG_K_BEGIN, FIG_K_EVAL, FIG_K_END, FIG_K_PROBE };   // sequential fill, begin, eval (items), end (list), probe (reach bits)
+
+// one persistent launch of kernel `k` with the class's LDS size
+template <typename... P, typename... Args>
+static hipError_t launch_one(void (*k)(P...), size_t lds, int nt, int blocks, hipStream_t stream, Args... args) {
+    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(nt), lds, stream, args...);
+    return hipGetLastError();
+}
+
+template <bool LDS_TAB, int NT>
+static hipError_t launch_kind(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, FigKind kind, int blocks, const void *list, int n, int qsel) {
+    const FigKernArgs A = fig_kargs_of(c.c, qsel, ctx->sh_on);
+    switch (kind) {
+        case FIG_K_FILL: return launch_one(fig_fill_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
+        case FIG_K_BEGIN: return launch_one(fig_begin_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
+        case FIG_K_PROBE: return launch_one(fig_probe_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
+        case FIG_K_EVAL: return launch_one(fig_eval_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A, (const int4 *)list, n);
+        case FIG_K_END: return launch_one(fig_end_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A, (const int *)list, n);
+    }
+    return hipErrorInvalidValue;
+}
+
+static hipError_t launch_any(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, FigKind kind, int blocks, const void *list, int n, int qsel = 0) {
+    if (c.c.tiles > 0) return launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);      // LDS-tiled: the LDS code path with a streamed table
+    if (c.c.lds_tab) return c.c.nt == 256 ? launch_kind<true, 256>(ctx, c, db, stream, kind, blocks, list, n, qsel) : launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);
+    return launch_kind<false, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);
+}
 
 extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     if (!ctx || !b) return FIG_EINVAL;
@@ -469,7 +418,7 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     ctx->str_total = K.str_total; ctx->n_gaps = ng;
     ctx->n_ureads = (int64_t)K.u_pos.size(); ctx->n_preads = (int64_t)K.p_pos.size();
     ctx->classes.clear();
-    int max_blocks = 1;
+    const bool log = fig_knobs_from_env(0).log;
     for (const FigLaunchClass &lc : K.classes) {
         fig_ctx::Cls c;
         c.c = lc;
@@ -477,8 +426,7 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
         per_cu = std::min(per_cu, 8);
         c.capacity = ctx->n_cu * per_cu;
         c.blocks = std::min<int>(lc.q_end - lc.q_begin, c.capacity);
-        max_blocks = std::max(max_blocks, c.capacity);
-        if (getenv("FIG_SCHED_LOG")) fprintf(stderr, "[figsched] class: capG=%d capGl=%d ncolE=%d Wcap=%d nt=%d nteams=%d lds_tab=%d tiles=%d tile_cols=%d lds=%zu gaps=%d per_cu=%d blocks=%d (FigState %zu B)\n",
+        if (log) fprintf(stderr, "[figsched] class: capG=%d capGl=%d ncolE=%d Wcap=%d nt=%d nteams=%d lds_tab=%d tiles=%d tile_cols=%d lds=%zu gaps=%d per_cu=%d blocks=%d (FigState %zu B)\n",
                                              lc.capG, lc.capGl, lc.ncolE, lc.Wcap, lc.nt, lc.nteams, (int)lc.lds_tab, lc.tiles, lc.tile_cols, lc.lds, lc.q_end - lc.q_begin, per_cu, c.blocks, sizeof(FigState));
         ctx->classes.push_back(c);
     }
@@ -520,7 +468,6 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     if ((rc = dev_alloc(ctx, 512, &p))) return rc; db.counters = (unsigned long long *)p;
     size_t total_blocks = 0;
     for (const fig_ctx::Cls &c : ctx->classes) total_blocks += (size_t)c.capacity;
-    (void)max_blocks;
     if ((rc = dev_alloc(ctx, (size_t)stride * std::max<size_t>(total_blocks, 1), &p))) return rc; db.scratch = (uint8_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)K.persist_total + 256, &p))) return rc; db.persist = (uint8_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1) * 16, &p))) return rc; db.gapctl = (int32_t *)p;
@@ -555,16 +502,7 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     ctx->stats.h2d_ms = ms;
     ctx->stats.packed_bytes = K.packed_bytes();
     ctx->have_batch = true;
-    if (!K.ot_given && m->partial_flag && ng > 0) {
-        // no carry given: the batch is ONE worker process of the reference taking its gaps in batch order -- measure which
-        // gaps get to Figbird.cpp:6317 and hand every gap the prefix-OR of its predecessors
-        std::vector<uint8_t> reach((size_t)ng, 0), preset((size_t)ng, 0);
-        if ((rc = fig_batch_probe_reach(ctx, reach.data()))) { free_batch(ctx); return rc; }
-        std::vector<int64_t> ids((size_t)ng);
-        for (int64_t g = 0; g < ng; g++) ids[(size_t)g] = g;
-        fig_ot_carry(ids, reach.data(), preset.data());
-        if ((rc = fig_batch_set_ot_preset(ctx, preset.data()))) { free_batch(ctx); return rc; }
-    }
+    if (!K.ot_given && m->partial_flag && ng > 0 && (rc = fig_ot_carry_measured(ctx, ng))) { free_batch(ctx); return rc; }
     return FIG_OK;
 }
 
@@ -578,13 +516,11 @@ extern "C" int fig_batch_probe_reach(fig_ctx *ctx, uint8_t *reach) {
     memset(reach, 0, (size_t)ng);
     if (!ctx->hm.partial_flag || ng == 0) return FIG_OK;
     FigDevBatch db = ctx->db;
-    db.dbg_n_cand = nullptr; db.dbg_cand_i = nullptr; db.dbg_cand_lik = nullptr; db.dbg_max_cand = 0; db.dbg_n_place = nullptr;
-    db.draw_pos = db.draw_isz = db.draw_len = nullptr;
-    db.dbg_counts = db.dbg_read_maxlv = nullptr; db.dbg_plane_cols = db.dbg_plane_reads = 0;
+    fig_batch_clear_planes(db);
     FIG_HIP(hipMemsetAsync(db.gapctl, 0, (size_t)ng * 16, ctx->stream));
     for (const fig_ctx::Cls &c : ctx->classes) {
         FIG_HIP(hipMemsetAsync(db.queue_head, 0, 8, ctx->stream));
-        FIG_HIP(launch_any(ctx, c, db, ctx->stream, 4, c.blocks, nullptr, 0));
+        FIG_HIP(launch_any(ctx, c, db, ctx->stream, FIG_K_PROBE, c.blocks, nullptr, 0));
     }
     std::vector<int32_t> ctl((size_t)ng * 4);
     FIG_HIP(hipMemcpyAsync(ctl.data(), db.gapctl, (size_t)ng * 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -604,159 +540,62 @@ extern "C" int fig_batch_set_ot_preset(fig_ctx *ctx, const uint8_t *preset) {
     return FIG_OK;
 }
 
-static FigKernArgs kargs_of(const fig_ctx::Cls &c) {
-    FigKernArgs A;
-    A.capG = c.c.capG; A.capGl = c.c.capGl; A.ncolE = c.c.ncolE; A.Wcap = c.c.Wcap; A.nteams = c.c.nteams;
-    A.q_begin = c.c.q_begin; A.q_end = c.c.q_end; A.qsel = 0;
-    A.tiles = c.c.tiles; A.tile_step = c.c.tile_step; A.tile_cols = c.c.tile_cols; A.tiled_max = c.c.tiled_max;
-    // FIG_ESTEP=pair: the pair-chain E-step everywhere (A/B runs, tests); FIG_SH_CHUNKS=<1..4>: chunks per super-chunk of the
-    // shared-factor E-step (fig_engine_shared.h; default 4: bench step 24.3 s with 2, 23.9 s with 4)
-    A.sh_on = 0;                       // set by launch_kind from the context (the environment is read once, at fig_ctx_create)
-    return A;
-}
-
-// kind: 0 sequential fill, 1 begin, 2 eval (items), 3 end (list), 4 probe (reach bits)
-template <bool LDS_TAB, int NT>
-static hipError_t launch_kind(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, int kind, int blocks, const void *list, int n, int qsel) {
-    FigKernArgs A = kargs_of(c);
-    A.qsel = qsel; A.sh_on = ctx->sh_on;
-    hipError_t e = hipSuccess;
-    if (kind == 0) {
-        auto k = fig_fill_kernel<LDS_TAB, NT>;
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.c.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(NT), c.c.lds, stream, ctx->dm, db, A);
-    } else if (kind == 1) {
-        auto k = fig_begin_kernel<LDS_TAB, NT>;
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.c.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(NT), c.c.lds, stream, ctx->dm, db, A);
-    } else if (kind == 2) {
-        auto k = fig_eval_kernel<LDS_TAB, NT>;
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.c.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(NT), c.c.lds, stream, ctx->dm, db, A, (const int4 *)list, n);
-    } else if (kind == 4) {
-        auto k = fig_probe_kernel<LDS_TAB, NT>;
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.c.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(NT), c.c.lds, stream, ctx->dm, db, A);
-    } else {
-        auto k = fig_end_kernel<LDS_TAB, NT>;
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.c.lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(NT), c.c.lds, stream, ctx->dm, db, A, (const int *)list, n);
-    }
-    return hipGetLastError();
-}
-
-static hipError_t launch_any(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, int kind, int blocks, const void *list, int n, int qsel) {
-    if (c.c.tiles > 0) return launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);      // LDS-tiled: the LDS code path with a streamed table
-    if (c.c.lds_tab) return c.c.nt == 256 ? launch_kind<true, 256>(ctx, c, db, stream, kind, blocks, list, n, qsel) : launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);
-    return launch_kind<false, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);
-}
-
 // Candidate-parallel scheduling of one class (see fig_engine_sched.h).  Host-driven rounds: begin -> {eval chunk,
-// replay}* -> end.  Returns the number of kernel launches, or -1 on a HIP error (ctx->last_hip set).
-static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln) {
+// replay}* -> end, every round as fig_plan_round (fig_abi_host.h) lays it out.  Returns the number of kernel launches, or
+// -1 on a HIP error (ctx->last_hip set).
+static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln, const FigKnobs &knobs) {
     FigDevBatch db = ctx->db;
     db.queue_head = ln.queue_head; db.scratch = ln.scratch;
     hipStream_t stream = ln.stream;
     hipSetDevice(ctx->device);
-    const int n_cls = c.c.q_end - c.c.q_begin;
     int nl = 0;
     hipError_t e;
     auto fail = [&](hipError_t er) { ctx->last_hip = (int)er; return -1; };
+    const int capacity = std::max(1, c.capacity);      // workgroups the device holds for this class (not capped by the gap count)
     // every persistent launch pops from one of the lane's two queue heads and zeroes the other for its successor
-    if ((e = launch_any(ctx, c, db, stream, 1, std::min(std::max(1, c.capacity), n_cls), nullptr, 0, ln.qsel)) != hipSuccess) return fail(e);
-    ln.qsel ^= 1;
-    nl++;
+    auto launch = [&](FigKind kind, int n_work, const void *list) {
+        hipError_t er = launch_any(ctx, c, db, stream, kind, std::min(capacity, n_work), list, n_work, ln.qsel);
+        ln.qsel ^= 1; nl++;
+        return er;
+    };
+    if ((e = launch(FIG_K_BEGIN, c.c.q_end - c.c.q_begin, nullptr)) != hipSuccess) return fail(e);
     int32_t *ctl = ln.h_ctl;
     const size_t ctl_n = (size_t)ctx->n_gaps * 4;
-    std::vector<int> ids(ctx->h_order.begin() + c.c.q_begin, ctx->h_order.begin() + c.c.q_end);   // cost-sorted
-    std::vector<int> items, entries, endlist;
-    const int slots_cap = ctx->nslots;
-    const int capacity = std::max(1, c.capacity);      // workgroups the device holds for this class (not capped by the gap count)
-    const bool log = getenv("FIG_SCHED_LOG") != nullptr;
-    const int minc = getenv("FIG_MIN_CHUNK") ? std::max(1, atoi(getenv("FIG_MIN_CHUNK"))) : 16;      // candidates per gap and round, at least
-    const double ipw_base = getenv("FIG_ITEMS_PER_WG") ? std::max(1.0, atof(getenv("FIG_ITEMS_PER_WG"))) : (ctx->dm.unmapped ? 12.0 : 6.0);  // items per resident workgroup and round (partial-mode pass, 8 192 gaps: 6 -> 4 052 gaps/s, 12 -> 3 887, 24 -> 3 875, 48 -> 3 668: shorter rounds discard fewer candidates past an early stop; unmapped, measured on the bench batch: 4 -> 34.4 s, 8 -> 29.7, 12 -> 29.1, 16 -> 29.2 per step)
+    const std::vector<int> ids(ctx->h_order.begin() + c.c.q_begin, ctx->h_order.begin() + c.c.q_end);   // cost-sorted
+    FigRound R;
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = now();
     double t_prev = now(); int round = 0, last_items = 0, last_active = 0, last_chunk = 0, n_active_max = 0;
     while (true) {
         if ((e = hipMemcpyAsync(ctl, db.gapctl, ctl_n * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);
-        int n_active = 0;
-        for (int g : ids) if (ctl[(size_t)g * 4] == 1) n_active++;
-        if (log) { double t = now(); fprintf(stderr, "[figsched] capG=%d round %d: active=%d chunk=%d items=%d blocks=%d  %.1f ms\n", c.c.capG, round, last_active, last_chunk, last_items, capacity, t - t_prev); t_prev = t; }
+        fig_plan_round(ids, ctl, capacity, c.c.nsplit, ctx->nslots, knobs.minc, knobs.ipw, n_active_max, R);
+        if (knobs.log) { double t = now(); fprintf(stderr, "[figsched] capG=%d round %d: active=%d chunk=%d items=%d blocks=%d  %.1f ms\n", c.c.capG, round, last_active, last_chunk, last_items, capacity, t - t_prev); t_prev = t; }
         round++;
-        if (n_active == 0) break;
-        // Candidates per gap this round: proportional to the candidates the gap still has, so that all gaps of the class
-        // finish in about the same round and every round carries ~12 items per resident workgroup (of both lanes of a split class).  A gap that stops
-        // early discards at most chunk-1 evaluations.
-        long long rem_total = 0;
-        for (int g : ids) if (ctl[(size_t)g * 4] == 1) rem_total += std::max(0, ctl[(size_t)g * 4 + 2] - ctl[(size_t)g * 4 + 1]);
-        // Round size: `ipw_base` items per resident workgroup while the lane has about a hundred active gaps (the 512-gap bench
-        // batch: 12 is its optimum), growing with the lane's number of active gaps (its maximum so far) up to 8x.  Measured on one box (round 3,
-        // profiles/round3/largefill_*): the 2048-gap fill of the bench recipe takes 111.9 s with 12 items per workgroup and
-        // round (121 rounds per lane of 1920 items over 385 active gaps: every round ends with a tail of the long items of
-        // the most expensive gaps), 99.8 s with 48 and 98.5 s with 96 -- while 48 costs the 512-gap batch 3 %.
-        n_active_max = std::max(n_active_max, n_active);
-        const double ipw = ipw_base * std::min(8.0, std::max(1.0, n_active_max / 96.0));      // by the lane's largest active set: the rounds stay long to the end of a big fill
-        const double share = rem_total > 0 ? (ipw * capacity / (double)std::max(1, c.c.nsplit)) / (double)rem_total : 1.0;
-        // Admission: a gap gets at least `minc` candidates in a round it takes part in, and gaps are admitted in cost order
-        // until the round is full.  With thousands of active gaps the proportional share alone would hand every gap a few
-        // candidates per round: hundreds of rounds per gap and, worse, hundreds of DIFFERENT gaps in flight at once, whose
-        // reads then miss the L2 (a 2048-gap fill ran at 0.33 of peak against 0.37 for 512 gaps).  Workgroups that pop
-        // neighbouring items work on the same gap's reads.
-        const double target = ipw * capacity / (double)std::max(1, c.c.nsplit);
-        long long total = 0;
-        int chunk = 0;
-        items.clear(); entries.clear();
-        for (int g : ids) {
-            if (ctl[(size_t)g * 4] != 1) continue;
-            if ((double)total >= 1.25 * target) break;           // the rest waits for a later round
-            int j = ctl[(size_t)g * 4 + 1], range = ctl[(size_t)g * 4 + 2];
-            int want = (int)std::ceil((range - j) * share);
-            want = std::max(minc, std::min(want, slots_cap));
-            want = std::min(want, slots_cap);
-            int n = std::min(want, range - j);
-            if (n <= 0) { n = 0; }                                // (replayed with nothing to evaluate: the replay closes the gap)
-            chunk = std::max(chunk, n);
-            total += n;
-            entries.push_back(g); entries.push_back(n); entries.push_back(0); entries.push_back(0);
-        }
-        // items gap-major in descending-cost gap order (longest processing time first keeps the round's tail short)
-        for (size_t q = 0; q < entries.size(); q += 4)
-            for (int k = entries[q + 1] - 1; k >= 0; k--) { int g = entries[q]; items.push_back(g); items.push_back(ctl[(size_t)g * 4 + 1] + k); items.push_back(k); items.push_back(0); }
-        if (ln.cap < items.size() || ln.cap < entries.size()) return fail(hipErrorOutOfMemory);
-        int n_items = (int)(items.size() / 4), n_ent = (int)(entries.size() / 4);
-        last_items = n_items; last_active = n_active; last_chunk = chunk;
+        if (R.n_active == 0) break;
+        if (ln.cap < R.items.size() || ln.cap < R.entries.size()) return fail(hipErrorOutOfMemory);
+        const int n_items = (int)(R.items.size() / 4), n_ent = (int)(R.entries.size() / 4);
+        last_items = n_items; last_active = R.n_active; last_chunk = R.chunk;
         if (n_items > 0) {
-            memcpy(ln.h_items, items.data(), items.size() * 4);
-            if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, items.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
-            if ((e = launch_any(ctx, c, db, stream, 2, std::min(capacity, n_items), ln.d_items, n_items, ln.qsel)) != hipSuccess) return fail(e);
-            ln.qsel ^= 1;
-            nl++;
+            memcpy(ln.h_items, R.items.data(), R.items.size() * 4);
+            if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, R.items.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+            if ((e = launch(FIG_K_EVAL, n_items, ln.d_items)) != hipSuccess) return fail(e);
         }
-        memcpy(ln.h_entries, entries.data(), entries.size() * 4);
-        if ((e = hipMemcpyAsync(ln.d_entries, ln.h_entries, entries.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+        memcpy(ln.h_entries, R.entries.data(), R.entries.size() * 4);
+        if ((e = hipMemcpyAsync(ln.d_entries, ln.h_entries, R.entries.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
         hipLaunchKernelGGL(fig_replay_kernel, dim3(n_ent), dim3(64), sizeof(FigState) + 64, stream, ctx->dm, db, (const int4 *)ln.d_entries, n_ent);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e);
         nl++;
     }
-    endlist.clear();
+    std::vector<int> endlist;
     for (int g : ids) if (ctl[(size_t)g * 4] == 2) endlist.push_back(g);
     if (!endlist.empty()) {
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);      // h_items is reused: the last round's upload must have left it
         memcpy(ln.h_items, endlist.data(), endlist.size() * 4);
         if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, endlist.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
-        if ((e = launch_any(ctx, c, db, stream, 3, std::min(capacity, (int)endlist.size()), ln.d_items, (int)endlist.size(), ln.qsel)) != hipSuccess) return fail(e);
-        ln.qsel ^= 1;
-        nl++;
-        if (log) { const double t0 = now(); hipStreamSynchronize(stream); fprintf(stderr, "[figsched] capG=%d end kernel: %d gaps, %.1f ms (lane done at %.1f ms since its first round)\n", c.c.capG, (int)endlist.size(), now() - t0, now() - t_start); }
+        if ((e = launch(FIG_K_END, (int)endlist.size(), ln.d_items)) != hipSuccess) return fail(e);
+        if (knobs.log) { const double t0 = now(); hipStreamSynchronize(stream); fprintf(stderr, "[figsched] capG=%d end kernel: %d gaps, %.1f ms (lane done at %.1f ms since its first round)\n", c.c.capG, (int)endlist.size(), now() - t0, now() - t_start); }
     }
-    (void)n_cls;
     return nl;
 }
 
@@ -770,9 +609,7 @@ extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
     std::vector<void *> tmp;
     auto talloc = [&](size_t n, void **p) -> int { if (hipMalloc(p, n ? n : 8) != hipSuccess) return FIG_ENOMEM; tmp.push_back(*p); return FIG_OK; };
     auto tfree = [&]() { for (void *p : tmp) hipFree(p); };
-    db.dbg_n_cand = nullptr; db.dbg_cand_i = nullptr; db.dbg_cand_lik = nullptr; db.dbg_max_cand = 0; db.dbg_n_place = nullptr;
-    db.draw_pos = db.draw_isz = db.draw_len = nullptr;
-    db.dbg_counts = db.dbg_read_maxlv = nullptr; db.dbg_plane_cols = db.dbg_plane_reads = 0;
+    fig_batch_clear_planes(db);
     void *p;
     if (out->dbg_n_cand && out->dbg_cand_i && out->dbg_cand_lik && out->dbg_max_cand > 0) {
         db.dbg_max_cand = out->dbg_max_cand;
@@ -809,13 +646,12 @@ extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
     hipMemsetAsync(db.gapctl, 0, (size_t)std::max<int64_t>(ng, 1) * 16, ctx->stream);
     hipEventRecord(ctx->ev0, ctx->stream);
     int nl = 0;
-    const char *sched = getenv("FIG_SCHED");
-    const bool seq = sched && strcmp(sched, "seq") == 0;
-    if (seq) {
+    const FigKnobs knobs = fig_knobs_from_env(ctx->dm.unmapped);      // read here, on the caller's thread: the lane threads only get the values
+    if (knobs.seq) {
         for (size_t ci = 0; ci < ctx->classes.size(); ci++) {
             const fig_ctx::Cls &c = ctx->classes[ci];
             hipMemsetAsync(db.queue_head, 0, 4, ctx->stream);
-            hipError_t e = launch_any(ctx, c, db, ctx->stream, 0, c.blocks, nullptr, 0);
+            hipError_t e = launch_any(ctx, c, db, ctx->stream, FIG_K_FILL, c.blocks, nullptr, 0);
             if (e != hipSuccess) { ctx->last_hip = (int)e; tfree(); return FIG_EHIP; }
             nl++;
         }
@@ -825,12 +661,11 @@ extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
         std::vector<int> rcs(nc, 0);
         ctx->db = db;
         for (size_t ci = 0; ci < nc; ci++) hipStreamWaitEvent(ctx->lanes[ci].stream, ctx->ev0, 0);
-        const char *ser = getenv("FIG_LANES");
-        if (nc <= 1 || (ser && strcmp(ser, "serial") == 0)) {
-            for (size_t ci = 0; ci < nc; ci++) rcs[ci] = run_class_parallel(ctx, ctx->classes[ci], ctx->lanes[ci]);
+        if (nc <= 1 || knobs.lanes_serial) {
+            for (size_t ci = 0; ci < nc; ci++) rcs[ci] = run_class_parallel(ctx, ctx->classes[ci], ctx->lanes[ci], knobs);
         } else {
             std::vector<std::thread> th;
-            for (size_t ci = 0; ci < nc; ci++) th.emplace_back([&, ci] { rcs[ci] = run_class_parallel(ctx, ctx->classes[ci], ctx->lanes[ci]); });
+            for (size_t ci = 0; ci < nc; ci++) th.emplace_back([&, ci] { rcs[ci] = run_class_parallel(ctx, ctx->classes[ci], ctx->lanes[ci], knobs); });
             for (auto &t : th) t.join();
         }
         for (size_t ci = 0; ci < nc; ci++) {
@@ -880,33 +715,16 @@ extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
       fprintf(stderr, "[figprof] raw slots:"); for (int i = 0; i < 22; i++) fprintf(stderr, " %d:%.1f", i, cnt[8 + i] / 1e9); for (int i = 22; i < 40; i++) fprintf(stderr, " %d:%.1f", i, cnt[32 + i - 22] / 1e9); fprintf(stderr, "\n");
       fprintf(stderr, "[figprof] barrier wait %.3f of %.3f wave-Gcycles = %.1f %%\n", cnt[30] / 1e9, cnt[31] / 1e9, cnt[31] ? 100.0 * cnt[30] / cnt[31] : 0.0); }
 #endif
-    if (getenv("FIG_SCHED_LOG")) fprintf(stderr, "[figsched] useful flops %.4g, speculative evaluations executed %.4g (%.1f %% discarded)\n", (double)cnt[1], (double)cnt[2], cnt[2] ? 100.0 * (1.0 - ((double)cnt[1] / (double)cnt[2])) : 0.0);
+    if (knobs.log) fprintf(stderr, "[figsched] useful flops %.4g, speculative evaluations executed %.4g (%.1f %% discarded)\n", (double)cnt[1], (double)cnt[2], cnt[2] ? 100.0 * (1.0 - ((double)cnt[1] / (double)cnt[2])) : 0.0);
     ctx->stats.place_calls = (int64_t)cnt[0];
     ctx->stats.alg_flops = (double)cnt[1];
     ctx->stats.spec_flops = (double)cnt[2];
     ctx->stats.mle_alg_flops = (double)cnt[3];
     ctx->stats.mle_exec_flops = (double)cnt[4];
-    // compact strings
-    int64_t need = 0;
-    for (int64_t g = 0; g < ng; g++) need += out->filled_len[g] > 0 ? out->filled_len[g] : 0;
-    if (need > out->str_capacity) return FIG_ENOSPC;
-    int64_t o = 0;
-    for (int64_t g = 0; g < ng; g++) {
-        out->str_off[g] = o;
-        int n = out->filled_len[g];
-        if (n > 0) { memcpy(out->str + o, hstr.data() + ctx->h_str_off[g], (size_t)n); o += n; }
-    }
-    out->str_off[ng] = o;
-    return FIG_OK;
+    return fig_compact_results(ng, hstr.data(), ctx->h_str_off.data(), out);
 }
 
-extern "C" int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) {
-    int rc = fig_batch_upload(ctx, batch);
-    if (rc) return rc;
-    rc = fig_fill_resident(ctx, out);
-    fig_batch_free(ctx);
-    return rc;
-}
+extern "C" int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) { return fig_fill_gaps_once(ctx, batch, out); }
 
 extern "C" int fig_get_stats(const fig_ctx *ctx, fig_stats *out) {
     if (!ctx || !out) return FIG_EINVAL;

@@ -1,0 +1,224 @@
+// fig_abi_host.h -- the host logic of the C ABI (include/figbird_hip.h) that does not touch a device: error strings, model
+// checks and tables, the environment knobs, the round planner of the candidate-parallel scheduler, result compaction.
+// Pure C++ (no HIP): compiled into libfighip.so (fig_abi.hip) and into the one-lane emulation the CPU tests run
+// (tests/emu/fig_emu_abi.cpp), so that every decision below is made in one place and the CPU suite checks the shipped code.
+#ifndef FIG_ABI_HOST_H
+#define FIG_ABI_HOST_H
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "../../include/figbird_hip.h"
+#include "fig_types.h"
+#include "fig_gaprules.h"
+// (fig_engine.h and fig_pack.h must already be included: FigKernArgs, FigLaunchClass and fig_model_fmm come from them)
+
+static inline const char *fig_strerror_text(int code) {
+    switch (code) {
+        case FIG_OK: return "ok";
+        case FIG_EINVAL: return "invalid argument";
+        case FIG_ENODEV: return "no usable HIP device (libfighip has no CPU path)";
+        case FIG_ENOMEM: return "out of memory";
+        case FIG_EHIP: return "HIP runtime error";
+        case FIG_ENOSPC: return "result string buffer too small";
+        case FIG_EUNSUP: return "input outside the supported envelope";
+        default: return "unknown error";
+    }
+}
+
+// ------------------------------------------------------------------------------------- model
+static inline int fig_model_check(const fig_model *m) {
+    if (!m || !m->error_pos_dist || !m->in_pos_dist || !m->del_pos_dist || !m->insert_len_dist_smoothed) return FIG_EINVAL;
+    if (m->max_read_length <= 0 || m->max_read_length > FIG_MAX_READLEN) return FIG_EUNSUP;
+    if (m->max_insert_size <= 0) return FIG_EINVAL;
+    if (m->partial_flag && m->unmapped_flag) return FIG_EUNSUP;      // the driver never sets both (RunFigbird.sh:211-216)
+    if (m->insert_threshold_min < 0 || m->insert_threshold_max >= m->max_insert_size + 1) return FIG_EINVAL;
+    return FIG_OK;
+}
+
+// Offsets (in doubles) of the model tables inside the one contiguous vector fig_model_tables() fills; every table starts
+// on a 64-byte boundary of it.
+struct FigModelOffsets { size_t e, pairs, m3, insd, qtab, ome; };
+
+// Fills `all` with the tables of FigDevModel and `dm` with its scalars.  The pointers of `dm` are set by
+// fig_model_point() once the caller knows where `all` lives (the device copy for libfighip, the vector itself for the
+// emulation).
+static void fig_model_tables(const fig_model *m, std::vector<double> &all, FigModelOffsets &o, FigDevModel &dm) {
+    const int L = m->max_read_length;
+    std::vector<double> h_e(m->error_pos_dist, m->error_pos_dist + L), h_ome(L), h_m3(L);
+    for (int k = 0; k < L; k++) {
+        volatile double a = 1 - m->error_pos_dist[k];                 // (1-errorPosDist[k])               Figbird.cpp:3160
+        h_ome[k] = a;
+        volatile double b = 1 - m->error_pos_dist[k] - m->in_pos_dist[k] - m->del_pos_dist[k];   // Figbird.cpp:3400
+        h_m3[k] = b;
+    }
+    std::vector<double> h_insd(m->insert_len_dist_smoothed, m->insert_len_dist_smoothed + m->max_insert_size);
+    h_insd.push_back(0.0);                                            // insertThresholdMax may equal maxInsertSize (:7194)
+    std::vector<double> h_qtab(256);
+    for (int c = 0; c < 256; c++) { int Q = c - 33; h_qtab[c] = pow(10, -Q / 10.0); }   // qualityFilter, :1791-1792
+    // pair tables for scalar loads: kt = {1-e[k], e[k]}, mt = {1-e-ins-del, e[k]}; the reversed copies serve
+    // reverse-strand reads (readIndex = len-1-j, Figbird.cpp:3569-3576) as rev[(L-len)+j]
+    std::vector<double> pairs((size_t)8 * L);
+    for (int k = 0; k < L; k++) {
+        pairs[2 * k] = h_ome[k]; pairs[2 * k + 1] = h_e[k];
+        pairs[2 * L + 2 * k] = h_ome[L - 1 - k]; pairs[2 * L + 2 * k + 1] = h_e[L - 1 - k];
+        pairs[4 * L + 2 * k] = h_m3[k]; pairs[4 * L + 2 * k + 1] = h_e[k];
+        pairs[6 * L + 2 * k] = h_m3[L - 1 - k]; pairs[6 * L + 2 * k + 1] = h_e[L - 1 - k];
+    }
+    all.clear();
+    o.e = 0; all.insert(all.end(), h_e.begin(), h_e.end()); while (all.size() % 8) all.push_back(0);
+    o.pairs = all.size(); all.insert(all.end(), pairs.begin(), pairs.end()); while (all.size() % 8) all.push_back(0);
+    o.m3 = all.size(); all.insert(all.end(), h_m3.begin(), h_m3.end()); while (all.size() % 8) all.push_back(0);
+    o.insd = all.size(); all.insert(all.end(), h_insd.begin(), h_insd.end()); while (all.size() % 8) all.push_back(0);
+    o.qtab = all.size(); all.insert(all.end(), h_qtab.begin(), h_qtab.end());
+    o.ome = all.size(); all.insert(all.end(), h_ome.begin(), h_ome.end());
+    dm.L = L; dm.Tmin = m->insert_threshold_min; dm.Tmax = m->insert_threshold_max; dm.cutoff = m->gap_prob_cutoff;
+    dm.partial_flag = m->partial_flag; dm.unmapped = m->unmapped_flag; dm.script_itr = m->script_itr; dm.D = m->max_distance;
+    dm.read_length = m->read_length; dm.neg_overlap = m->neg_overlap; dm.partial_len = m->partial_len; dm.unm_limit = m->unm_limit;
+    dm.max_insert = m->max_insert_size;
+    for (int i = 0; i < 25; i++) dm.T[i] = m->error_type_probs[i];
+    dm.fmm_up = fig_model_fmm(m);
+}
+
+static inline void fig_model_point(FigDevModel &dm, const FigModelOffsets &o, const double *d) {
+    dm.e = d + o.e; dm.ome = d + o.pairs; dm.m3 = d + o.m3; dm.insd = d + o.insd; dm.qtab = d + o.qtab;
+    dm.ome1 = d + o.ome;
+}
+
+// ------------------------------------------------------------------------------------- batch
+// the optional debug / draw planes of a fill: absent unless the call that launches sets them
+static inline void fig_batch_clear_planes(FigDevBatch &db) {
+    db.dbg_n_cand = nullptr; db.dbg_cand_i = nullptr; db.dbg_cand_lik = nullptr; db.dbg_max_cand = 0; db.dbg_n_place = nullptr;
+    db.draw_pos = db.draw_isz = db.draw_len = nullptr;
+    db.dbg_counts = db.dbg_read_maxlv = nullptr; db.dbg_plane_cols = db.dbg_plane_reads = 0;
+}
+
+// the launch arguments of a class (FigKernArgs, fig_engine.h)
+static FigKernArgs fig_kargs_of(const FigLaunchClass &c, int qsel, int sh_on) {
+    FigKernArgs A;
+    A.capG = c.capG; A.capGl = c.capGl; A.ncolE = c.ncolE; A.Wcap = c.Wcap; A.nteams = c.nteams;
+    A.q_begin = c.q_begin; A.q_end = c.q_end; A.qsel = qsel;
+    A.tiles = c.tiles; A.tile_step = c.tile_step; A.tile_cols = c.tile_cols; A.tiled_max = c.tiled_max;
+    A.sh_on = sh_on;
+    return A;
+}
+
+// An upload without fig_gap_batch::gap_ot_preset in partial mode: the batch is ONE worker process of the reference taking
+// its gaps in batch order -- measure which gaps get to Figbird.cpp:6317 and hand every gap the prefix-OR of its
+// predecessors.  Written on the two public calls, which both builds define.
+static int fig_ot_carry_measured(fig_ctx *ctx, int64_t ng) {
+    std::vector<uint8_t> reach((size_t)ng, 0), preset((size_t)ng, 0);
+    int rc;
+    if ((rc = fig_batch_probe_reach(ctx, reach.data()))) return rc;
+    std::vector<int64_t> ids((size_t)ng);
+    for (int64_t g = 0; g < ng; g++) ids[(size_t)g] = g;
+    fig_ot_carry(ids, reach.data(), preset.data());
+    return fig_batch_set_ot_preset(ctx, preset.data());
+}
+
+// Result strings: from one slot per gap at src_off[g] (`src`) to back-to-back in out->str, with out->str_off.
+static int fig_compact_results(int64_t ng, const char *src, const int64_t *src_off, fig_gap_results *out) {
+    int64_t need = 0;
+    for (int64_t g = 0; g < ng; g++) need += out->filled_len[g] > 0 ? out->filled_len[g] : 0;
+    if (need > out->str_capacity) return FIG_ENOSPC;
+    int64_t o = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        out->str_off[g] = o;
+        int n = out->filled_len[g];
+        if (n > 0) { memcpy(out->str + o, src + src_off[g], (size_t)n); o += n; }
+    }
+    out->str_off[ng] = o;
+    return FIG_OK;
+}
+
+// fig_fill_gaps: upload + fill + free, on the public calls
+static int fig_fill_gaps_once(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) {
+    int rc = fig_batch_upload(ctx, batch);
+    if (rc) return rc;
+    rc = fig_fill_resident(ctx, out);
+    fig_batch_free(ctx);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------- knobs
+// Every environment variable the ABI layer reads, in one place.  The scheduling knobs hold for one fig_fill_resident call:
+// it reads them on the calling thread before any lane thread starts and passes them down.  sh_on holds for a context
+// (the value read at fig_ctx_create).  fig_batch_upload reads `log` for its class listing.
+struct FigKnobs {
+    bool seq;            // FIG_SCHED=seq: whole gaps, one workgroup each
+    bool lanes_serial;   // FIG_LANES=serial: the class lanes one after the other on the calling thread
+    bool log;            // FIG_SCHED_LOG
+    int minc;            // FIG_MIN_CHUNK: candidates per gap and round, at least
+    double ipw;          // FIG_ITEMS_PER_WG: items per resident workgroup and round (partial-mode pass, 8 192 gaps: 6 -> 4 052 gaps/s, 12 -> 3 887, 24 -> 3 875, 48 -> 3 668: shorter rounds discard fewer candidates past an early stop; unmapped, measured on the bench batch: 4 -> 34.4 s, 8 -> 29.7, 12 -> 29.1, 16 -> 29.2 per step)
+    // FIG_ESTEP=pair: the pair-chain E-step everywhere (A/B runs, tests); FIG_SH_CHUNKS=<1..4>: chunks per super-chunk of the
+    // shared-factor E-step (fig_engine_shared.h; default 4: bench step 24.3 s with 2, 23.9 s with 4)
+    int sh_on;
+};
+
+static FigKnobs fig_knobs_from_env(int unmapped) {
+    FigKnobs k;
+    const char *sched = getenv("FIG_SCHED"), *ser = getenv("FIG_LANES"), *mc = getenv("FIG_MIN_CHUNK"), *ipw = getenv("FIG_ITEMS_PER_WG");
+    const char *ev = getenv("FIG_ESTEP"), *sc = getenv("FIG_SH_CHUNKS");
+    k.seq = sched && strcmp(sched, "seq") == 0;
+    k.lanes_serial = ser && strcmp(ser, "serial") == 0;
+    k.log = getenv("FIG_SCHED_LOG") != nullptr;
+    k.minc = mc ? std::max(1, atoi(mc)) : 16;
+    k.ipw = ipw ? std::max(1.0, atof(ipw)) : (unmapped ? 12.0 : 6.0);
+    k.sh_on = (ev && !strcmp(ev, "pair")) ? 0 : (sc ? std::max(1, std::min(FIG_SH_SC, atoi(sc))) : FIG_SH_SC);
+    return k;
+}
+
+// ------------------------------------------------------------------------------------- round planner
+// One round of the candidate-parallel scheduler (fig_engine_sched.h) for one class lane: which active gaps take part and
+// how many candidates each of them evaluates.  entries = {gap, n slots, 0, 0} per admitted gap (one replay each), items =
+// {gap, candidate index j, slot, 0} per evaluation.
+struct FigRound { std::vector<int> items, entries; int chunk = 0, n_active = 0; };
+
+// ids: the lane's gaps in cost order; ctl: gapctl snapshot ({status, next j, range, -} per gap of the batch); capacity:
+// workgroups the device holds for this class; nsplit: lanes the class runs as; slots_cap: candidate slots per gap;
+// n_active_max: the lane's largest active set so far (in/out).  n_active == 0 on return: nothing left, no round.
+static void fig_plan_round(const std::vector<int> &ids, const int32_t *ctl, int capacity, int nsplit, int slots_cap, int minc, double ipw_base,
+                           int &n_active_max, FigRound &R) {
+    std::vector<int> &items = R.items, &entries = R.entries;
+    items.clear(); entries.clear();
+    R.chunk = 0; R.n_active = 0;
+    for (int g : ids) if (ctl[(size_t)g * 4] == 1) R.n_active++;
+    if (R.n_active == 0) return;
+    // Candidates per gap this round: proportional to the candidates the gap still has, so that all gaps of the class
+    // finish in about the same round and every round carries ~12 items per resident workgroup (of both lanes of a split class).  A gap that stops
+    // early discards at most chunk-1 evaluations.
+    long long rem_total = 0;
+    for (int g : ids) if (ctl[(size_t)g * 4] == 1) rem_total += std::max(0, ctl[(size_t)g * 4 + 2] - ctl[(size_t)g * 4 + 1]);
+    // Round size: `ipw_base` items per resident workgroup while the lane has about a hundred active gaps (the 512-gap bench
+    // batch: 12 is its optimum), growing with the lane's number of active gaps (its maximum so far) up to 8x.  Measured on one box (round 3,
+    // profiles/round3/largefill_*): the 2048-gap fill of the bench recipe takes 111.9 s with 12 items per workgroup and
+    // round (121 rounds per lane of 1920 items over 385 active gaps: every round ends with a tail of the long items of
+    // the most expensive gaps), 99.8 s with 48 and 98.5 s with 96 -- while 48 costs the 512-gap batch 3 %.
+    n_active_max = std::max(n_active_max, R.n_active);
+    const double ipw = ipw_base * std::min(8.0, std::max(1.0, n_active_max / 96.0));      // by the lane's largest active set: the rounds stay long to the end of a big fill
+    const double share = rem_total > 0 ? (ipw * capacity / (double)std::max(1, nsplit)) / (double)rem_total : 1.0;
+    // Admission: a gap gets at least `minc` candidates in a round it takes part in, and gaps are admitted in cost order
+    // until the round is full.  With thousands of active gaps the proportional share alone would hand every gap a few
+    // candidates per round: hundreds of rounds per gap and, worse, hundreds of DIFFERENT gaps in flight at once, whose
+    // reads then miss the L2 (a 2048-gap fill ran at 0.33 of peak against 0.37 for 512 gaps).  Workgroups that pop
+    // neighbouring items work on the same gap's reads.
+    const double target = ipw * capacity / (double)std::max(1, nsplit);
+    long long total = 0;
+    for (int g : ids) {
+        if (ctl[(size_t)g * 4] != 1) continue;
+        if ((double)total >= 1.25 * target) break;           // the rest waits for a later round
+        int j = ctl[(size_t)g * 4 + 1], range = ctl[(size_t)g * 4 + 2];
+        int want = (int)std::ceil((range - j) * share);
+        want = std::min(std::max(want, minc), slots_cap);
+        int n = std::max(0, std::min(want, range - j));       // (0: replayed with nothing to evaluate: the replay closes the gap)
+        R.chunk = std::max(R.chunk, n);
+        total += n;
+        entries.push_back(g); entries.push_back(n); entries.push_back(0); entries.push_back(0);
+    }
+    // items gap-major in descending-cost gap order (longest processing time first keeps the round's tail short)
+    for (size_t q = 0; q < entries.size(); q += 4)
+        for (int k = entries[q + 1] - 1; k >= 0; k--) { int g = entries[q]; items.push_back(g); items.push_back(ctl[(size_t)g * 4 + 1] + k); items.push_back(k); items.push_back(0); }
+}
+
+#endif

@@ -297,6 +297,46 @@ struct FigEng {
     unsigned long long prof[40];     // FIG_PROF only: phase timers
 };
 
+// What a launch hands its workgroups besides model and batch: the class's capacities and memory form, the queue range.
+struct FigKernArgs { int capG, capGl, ncolE, Wcap, nteams, q_begin, q_end, qsel, tiles, tile_step, tile_cols, tiled_max, sh_on; };
+
+// LDS / slab carve-up of a workgroup (doubles first so everything stays 8-byte aligned):
+//   LDS table:  PQ[4][ncolE] (16 B each)  Q4[ncolE]  wbuf[nteams][Wcap]  | FigState  gs[capGl]  rb[FIG_MAX_READLEN+8]  plb
+//   LDS-tiled:  table tile [4][tile_cols] + Q4 tile  wbuf[nteams][Wcap]  | ...        (full table in the slab)
+//   slab table: nothing in front of FigState                                          (table and weights in the slab)
+// Pure arithmetic on {M, A, lds_tab}; the caller has set what depends on the launch (tid/nt/lane/wave/nw/wsz, E.scr).
+// Returns the bytes of LDS the layout occupies.
+FIG_D long long fig_eng_carve(FigEng &E, const FigDevModel &M, const FigKernArgs &A, bool lds_tab) {
+    E.capG = A.capG;
+    E.ncolE = A.ncolE; E.xoff = M.L - 1; E.Wcap = A.Wcap; E.nteams = A.nteams; E.sh_on = A.sh_on;
+    long long off = 0;
+    E.pq_lds = lds_tab; E.w_lds = lds_tab;
+    E.tiles = A.tiles; E.tile_step = A.tile_step; E.tile_cols = A.tile_cols;
+    if (lds_tab && A.tiles > 0) {
+        // LDS-tiled class: LDS = {table tile [4][tile_cols] + Q4 tile, weight rows}; the full table, and the buffers of the
+        // MLE pass (which runs its HBM-table form), stay in the scratch slab
+        E.pq_lds = 0;
+        E.off_pq = 0; E.off_q4 = 8 * A.tile_cols; E.off_w = 9 * A.tile_cols;
+        off = 9LL * A.tile_cols + (long long)A.nteams * A.Wcap;
+        { const long long mle = FIG_TILED_MLE_DOUBLES(A.ncolE, (int)E.nw); if (mle > off && mle <= A.tiled_max) off = mle; }   // as fig_pack sized it
+        E.pq = E.scr.pqg; E.q4 = E.scr.q4g; E.wbuf = E.scr.wg;
+    } else if (lds_tab) {
+        E.off_pq = 0; E.off_q4 = 8 * A.ncolE; E.off_w = 9 * A.ncolE;
+        off = 9LL * A.ncolE + (long long)A.nteams * A.Wcap;
+        E.pq = (FigPQ *)(fig_lds + E.off_pq); E.q4 = fig_lds + E.off_q4; E.wbuf = fig_lds + E.off_w;
+    } else {
+        E.off_pq = E.off_q4 = E.off_w = 0;
+        E.pq = E.scr.pqg; E.q4 = E.scr.q4g; E.wbuf = E.scr.wg;
+    }
+    E.S = (FigState *)(fig_lds + off); E.lds_tw = (int)off;
+    unsigned char *bp = (unsigned char *)(E.S + 1);
+    E.gs = bp; bp += ((A.capGl + 7) & ~7);
+    E.rb = bp; bp += ((FIG_MAX_READLEN + 8 + 15) & ~15);
+    E.plb = (uint32_t *)bp; E.off_plb = (int)((double *)bp - fig_lds);
+    E.kt_fwd = M.ome; E.kt_rev = M.ome + 2 * M.L; E.mt_fwd = M.ome + 4 * M.L; E.mt_rev = M.ome + 6 * M.L;
+    return off * 8 + (long long)sizeof(FigState) + ((A.capGl + 7) & ~7) + ((FIG_MAX_READLEN + 8 + 15) & ~15) + FIG_PLB_BYTES;
+}
+
 // ---------------------------------------------------------------------------------------
 // packed read access
 FIG_D int fig_read_code(const uint32_t *packed, long long woff, int len, int j) {

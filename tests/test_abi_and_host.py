@@ -255,3 +255,78 @@ def test_library_measures_the_carry_itself_without_a_preset(tmp_path):
         outs.append((res.filled_len.tolist(), res.gaptofill.tolist(), res.strings))
     assert outs[0] == outs[1]
     assert outs[0][0] == [int(e[4]) for e in exp] and outs[0][2] == [e[5] if len(e) > 5 else "" for e in exp]
+
+
+def _plan_round(lib, ids, ctl, capacity, nsplit, slots_cap, minc, ipw, n_active_max):
+    ids_a = np.asarray(ids, dtype=np.int32); ctl_a = np.asarray(ctl, dtype=np.int32).reshape(-1)
+    cap_ints = 4 * (len(ids) * (slots_cap + 1) + 1)
+    items = np.zeros(cap_ints, dtype=np.int32); entries = np.zeros(cap_ints, dtype=np.int32)
+    nam, n_items, n_ent, chunk = (ctypes.c_int(v) for v in (n_active_max, 0, 0, 0))
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    lib.fig_emu_plan_round.restype = ctypes.c_int
+    lib.fig_emu_plan_round.argtypes = [i32p, ctypes.c_int, i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                       ctypes.POINTER(ctypes.c_int), i32p, ctypes.POINTER(ctypes.c_int), i32p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    n_active = lib.fig_emu_plan_round(ids_a.ctypes.data_as(i32p), len(ids), ctl_a.ctypes.data_as(i32p), capacity, nsplit, slots_cap, minc, ipw, ctypes.byref(nam),
+                                      items.ctypes.data_as(i32p), ctypes.byref(n_items), entries.ctypes.data_as(i32p), ctypes.byref(n_ent), cap_ints, ctypes.byref(chunk))
+    assert n_active >= 0
+    return n_active, nam.value, items[:4 * n_items.value].reshape(-1, 4).tolist(), entries[:4 * n_ent.value].reshape(-1, 4).tolist(), chunk.value
+
+
+def _check_round(lib, ids, ctl, capacity, nsplit, slots_cap, minc, ipw, n_active_max):
+    """One planned round against what the scheduler promises; every expected value comes from the inputs."""
+    n_active, nam, items, entries, chunk = _plan_round(lib, ids, ctl, capacity, nsplit, slots_cap, minc, ipw, n_active_max)
+    active = [g for g in ids if ctl[g][0] == 1]                               # in cost order
+    assert n_active == len(active)
+    assert nam == max(n_active_max, len(active))                              # only grows
+    if not active:
+        assert items == [] and entries == []
+        return entries
+    target = ipw * min(8.0, max(1.0, nam / 96.0)) * capacity / max(1, nsplit)
+    assert [e[0] for e in entries] == active[:len(entries)] and len(entries) >= 1      # a prefix of the cost order
+    total, pos = 0, 0
+    for g, n, _, _ in entries:
+        assert total < 1.25 * target                                          # admitted while the round was not full
+        j, rng = ctl[g][1], ctl[g][2]
+        assert min(minc, slots_cap, rng - j) <= n <= min(slots_cap, rng - j)
+        if rng == j:
+            assert n == 0                                                     # replayed with nothing to evaluate
+        assert items[pos:pos + n] == [[g, j + k, k, 0] for k in range(n - 1, -1, -1)]      # contiguous, slots descending to 0
+        total += n; pos += n
+    assert pos == len(items)                                                  # no item without an entry
+    if len(entries) < len(active):
+        assert total >= 1.25 * target                                         # the rest waits only because the round is full
+    assert chunk == max(e[1] for e in entries)
+    return entries
+
+
+def test_round_planner_of_the_candidate_parallel_scheduler():
+    """fig_plan_round (fig_abi_host.h) is what libfighip's class lanes and the emulation both run; here it is driven on
+    hand-made gapctl snapshots through the emulation library's test-only shim."""
+    lib = ctypes.CDLL(util.EMULIB)
+    # gapctl rows {status, next j, range, -}: finished, active, loop done, active with nothing left, active near its end
+    ctl = [[0, 0, 0, 0], [1, 0, 40, 0], [2, 7, 7, 0], [1, 9, 9, 0], [1, 30, 33, 0], [1, 2, 200, 0]]
+    ent = _check_round(lib, [5, 1, 4, 3, 2, 0], ctl, capacity=4, nsplit=1, slots_cap=32, minc=16, ipw=12.0, n_active_max=0)
+    assert [e[:2] for e in ent] == [[5, 32], [1, 16], [4, 3], [3, 0]]          # share 48/241: every want below minc except the first
+    # nothing active: no round, and the lane's largest active set is kept
+    assert _plan_round(lib, [2, 0], ctl, 4, 1, 32, 16, 12.0, 5)[:2] == (0, 5)
+    # admission cut-off: 300 active gaps on two lanes of 8 workgroups; the round is full long before the last gap
+    big = [[1, g % 7, 40 + g % 5, 0] for g in range(300)]
+    ent = _check_round(lib, list(range(299, -1, -1)), big, capacity=8, nsplit=2, slots_cap=32, minc=16, ipw=12.0, n_active_max=0)
+    assert 1 < len(ent) < 300
+    # a chunk above the slot cap is clamped to it (the emulation's FIG_EMU_CHUNK form: exactly min(n, nslots, range - j))
+    ent = _check_round(lib, [1, 4, 5], ctl, capacity=1000, nsplit=1, slots_cap=3, minc=3, ipw=12.0, n_active_max=0)
+    assert [e[1] for e in ent] == [3, 3, 3]
+    ent = _check_round(lib, [1, 4, 5], ctl, capacity=1000, nsplit=1, slots_cap=32, minc=64, ipw=12.0, n_active_max=0)
+    assert [e[1] for e in ent] == [32, 3, 32]
+    # random snapshots, the lane's history carried from round to round
+    rng = np.random.default_rng(5)
+    nam = 0
+    for _ in range(50):
+        n = int(rng.integers(1, 400))
+        snap = [[int(rng.integers(0, 3)), 0, 0, 0] for _ in range(n)]
+        for row in snap:
+            row[2] = int(rng.integers(1, 120)); row[1] = int(rng.integers(0, row[2] + 1))
+        ids = [int(g) for g in rng.permutation(n)[:int(rng.integers(1, n + 1))]]
+        args = dict(capacity=int(rng.integers(1, 64)), nsplit=int(rng.integers(1, 3)), slots_cap=int(rng.integers(1, 65)), minc=int(rng.integers(1, 40)), ipw=float(rng.choice([6.0, 12.0])))
+        _check_round(lib, ids, snap, n_active_max=nam, **args)
+        nam = max(nam, sum(1 for g in ids if snap[g][0] == 1))

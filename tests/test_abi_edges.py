@@ -77,6 +77,15 @@ def _edge_checks(lib_path, tmp_path):
     eng.set_model(eng._model)
     with pytest.raises(RuntimeError, match="invalid argument"):
         eng.fill_resident()
+    # model descriptors both libraries refuse with the same check: a missing table, an empty insert-size table, an upper
+    # insert threshold past the table's zero pad.  The context keeps the model it had.
+    model = eng._model
+    for field, value in (("in_pos_dist", None), ("max_insert_size", 0), ("insert_threshold_max", len(model.insd) + 1)):
+        cm = model.cstruct()
+        setattr(cm, field, value)
+        with pytest.raises(RuntimeError, match="invalid argument"):
+            eng.set_model_struct(cm)
+    eng.set_model(model)
     # the engine is still usable after the errors and gives the same answer as before them
     r1 = eng.fill(batch)
     r2 = eng.fill(batch)
