@@ -8,6 +8,7 @@ import pytest
 
 import util
 from figbird_amd import api, synth
+from tools.fuzz_ref import READLEN_SWEEP
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +28,11 @@ def test_figfill_on_gpu_matches_reference_outputs(name, tmp_path):
         assert util.read(os.path.join(root, "tmp", fn)) == util.read(os.path.join(root, "ref", fn)), fn
 
 
-@pytest.mark.parametrize("name", ["unmapped_small", "unmapped_mid_err", "bench_b25", "bench_c1100"])
+@pytest.mark.parametrize("name", ["unmapped_small", "unmapped_mid_err", "bench_b25", "bench_c1100", "unmapped_L75"])
 def test_pair_chain_estep_still_matches_reference_outputs(name, tmp_path):
     """FIG_ESTEP=pair: the pair-chain E-step (fig_hot_estep) everywhere -- the form the 1217-1600-column class, candidates over
-    875 bp and clipped gaps still take -- on fixtures the default build fills through the shared-factor form: same bytes."""
+    875 bp and clipped gaps still take -- on fixtures the default build fills through the shared-factor form: same bytes.
+    unmapped_L75: a read length with L % 4 == 3, the one-base tail of either chain."""
     root = util.extract_golden(name, str(tmp_path))
     r = util.run([util.FIGFILL] + util.meta(root)["fillgaps_argv"], root, {"FIG_ESTEP": "pair"})
     assert r.returncode == 0, r.stderr
@@ -81,6 +83,46 @@ def test_gpu_fuzz_against_oracle(seed, tmp_path):
     from tools.fuzz_ref import mk
     from tools.compare_emu import run_one
     assert run_one(mk(seed), str(tmp_path), exe=util.FIGFILL, verbose=False)
+
+
+@pytest.mark.parametrize("L", READLEN_SWEEP)
+@pytest.mark.parametrize("mode", ["partial", "unmapped"])
+def test_gpu_read_length_sweep_against_oracle(mode, L, tmp_path):
+    """Read length as a dimension (tests/test_read_lengths.py has the same sweep for the emulation): either side of the partial
+    E-step's two-tile / four-tile switch (129 | 130), of its row strides (L % 8 == 7, L % 16 == 0), every L % 4 of the
+    shared-factor chain's tail, the pair form below L = 32 and the buffers sized for L = 200 -- output files, placeReads calls
+    and algorithmic flops equal the oracle's.  From L = 128 up most of these cases lie outside the domain on which the
+    reference itself is defined (oracle/README.md); there the oracle is the definition."""
+    from tools.fuzz_ref import mk_readlen
+    from tools.compare_emu import run_one
+    assert run_one(mk_readlen(mode, L), str(tmp_path), exe=util.FIGFILL, verbose=False, trace=True)
+
+
+@pytest.mark.parametrize("name", ["partial_L150", "unmapped_L75"])
+def test_planes_at_the_new_read_lengths_within_1e6(name, tmp_path):
+    """countsGap and the per-read E-step maxima of every candidate against the oracle's level-3 trace, at the tolerance
+    tests/test_planes.py states (1e-6 relative: device libm against glibc; 0 and +-inf exact): the four-tile partial E-step
+    (L = 150) and the chain's odd tail (L = 75)."""
+    from test_planes import check_planes
+    assert check_planes(None, name, tmp_path, tol=1e-6) > 0
+
+
+@pytest.mark.parametrize("name", ["partial_L150", "partial_L199"])
+@pytest.mark.parametrize("sched", ["seq", "spec"])
+def test_long_read_partial_goldens_in_both_workgroup_sizes_and_schedulers(name, sched, tmp_path):
+    """fig_partial_fast refuses a workgroup of fewer than 4 waves (or a wave count that is no multiple of 4) on the device only.
+    By the class table in fig_pack.h no placeReads call can run in such a workgroup: a gap whose longest candidate is <= 448
+    columns runs in 256 threads (4 waves), every other in 512 (8 waves); the one-wave replay kernel places no reads.  So the
+    guard is not reachable through the ABI, and what these fixtures pin is the fast form at both sizes it does run at:
+      partial_L150: 310 bp (one candidate, 310 columns) -> 4 waves; 50 bp (candidates to 3 L = 450), 160 bp (to 5 x 160 = 800)
+                    and 600 bp -> 8 waves;
+      partial_L199: 408 bp -> 4 waves; 209 bp (to 1045 columns) and 600 bp -> 8 waves.
+    Both through the speculative scheduler and the plain one-workgroup-per-gap kernel (FIG_SCHED=seq): the reference's bytes."""
+    root = util.extract_golden(name, str(tmp_path))
+    r = util.run([util.FIGFILL] + util.meta(root)["fillgaps_argv"], root, {"FIG_SCHED": sched})
+    assert r.returncode == 0, r.stderr
+    for fn in util.ref_files(root):
+        assert util.read(os.path.join(root, "tmp", fn)) == util.read(os.path.join(root, "ref", fn)), fn
 
 
 @pytest.mark.parametrize("name", util.BENCH_GOLDENS)

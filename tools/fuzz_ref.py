@@ -48,6 +48,59 @@ def mk_mid(seed):
                            read_n_rate=rnd.choice([0, 0.01]), script_itr=1)
 
 
+# ---- read length as a dimension (tests/test_read_lengths.py, tests/test_gpu_parity.py) -------------------------------------
+# L picks device code: the partial E-step's tile count (<LDS,2> up to L = 129, <LDS,4> for 130-200), its row strides (L % 8,
+# L % 16), the shared-factor chain's tail (L % 4), the pair form below L = 32, and the buffers sized for FIG_MAX_READLEN = 200.
+READLEN_SWEEP = [31, 32, 35, 63, 64, 75, 127, 128, 129, 130, 143, 144, 151, 199, 200]
+REF_MAX_HANG = 104          # oracle/README.md, "Read-length domain": partial_left[100] / partial_right[100], Figbird.cpp:1625
+
+
+def mk_readlen(mode, L, seed=None):
+    """One small case per (mode, L): two gaps, low coverage (seconds for the CPU oracle and the one-lane emulation), reads placed
+    in both gaps.  partial: a gap of L + 10 bp (candidate lengths 0 .. 5 (L + 10), Figbird.cpp:6886: both sides of the E-step's
+    G = 128 TS switch, for TS = 2 and TS = 4 alike) and one of 600 bp (one candidate length, left and right tile groups apart).
+    unmapped: 600 bp (one candidate length) next to 12 bp (up to 3 L candidate lengths, which the CPU can afford up to L = 75)
+    or 450 bp, with the frag library's clipped reads alongside: every candidate runs the chain whose tail L % 4 selects."""
+    seed = 900 + L if seed is None else seed
+    if mode == "partial":
+        gaps, pos = [], 1500
+        for g in (L + 10, 600):
+            gaps.append((pos, g)); pos += g + 1200
+        return synth.make_case(f"rl_p{L}", seed, "partial", gaps, contig_len=pos + 300, read_len=L, insert_mean=max(180, 2 * L + 40),
+                               insert_sd=10, coverage=4, err=0.005, n_model_pairs=400)
+    gaps, pos = [], 1500
+    for g in ((12, 600) if L <= 75 else (450, 600)):
+        gaps.append((pos, g)); pos += g + 1300
+    return synth.make_case(f"rl_u{L}", seed, "unmapped", gaps, contig_len=pos + 200, read_len=L, insert_mean=600, insert_sd=30,
+                           coverage=8, err=0.005, n_model_pairs=400, partial_reads_in_unmapped=True)
+
+
+def max_hang(case):
+    """The most bases any clipped (partial) read of the case hangs into its gap, capped by the gap's longest candidate length:
+    what the reference indexes partial_left / partial_right with (Figbird.cpp:1974-2009, :2053-2084)."""
+    worst = 0
+    for g in case.gaps:
+        gmax = max(g.length, int(2.5 * g.length)) if g.length <= 400 else g.length
+        if case.mode == "unmapped" and g.length < 30:
+            gmax = max(gmax, 70)
+        for r in g.partial:
+            hang = len(r.seq) - r.clipped_index - 1 if r.match in (1, 4) else r.clipped_index
+            worst = max(worst, min(hang, gmax))
+    return worst
+
+
+def ref_defined(case):
+    """Is the reference's own behaviour defined on this case (oracle/README.md, "Read-length domain")?"""
+    return max_hang(case) <= REF_MAX_HANG and case.read_len < 200      # char[MAX_READLENGTH = 200] holds 199 bases, Figbird.cpp:2544
+
+
+def clip_hang(case, limit=REF_MAX_HANG):
+    """Drop the clipped reads that hang more than `limit` bases into their gap: what is left is inside the reference's domain."""
+    for g in case.gaps:
+        g.partial = [r for r in g.partial if (len(r.seq) - r.clipped_index - 1 if r.match in (1, 4) else r.clipped_index) <= limit]
+    return case
+
+
 def one(seed):
     base = tempfile.mkdtemp(prefix=f"figfz{seed}_")
     try:

@@ -56,6 +56,20 @@ CASES = {
                      n_model_pairs=600, neg_overlap_gaps={0: (10, 14)}),
     "ot_carry_t3": dict(seed=5, mode="partial", gap_specs=[(1500, 10), (3000, 30), (4400, 45), (5940, 52)], contig_len=6000, insert_mean=180, insert_sd=10,
                         coverage=30, err=0.003, n_model_pairs=600, neg_overlap_gaps={0: (10, 14)}),
+    # ---- read length as a dimension (oracle/README.md, "Read-length domain").  Partial mode at L = 150 and at FIG_MAX_READLEN =
+    # MAX_READLENGTH = 200: the partial E-step's four-tile instantiation, its G = 128 TS = 512 switch (candidates of the 50-bp and
+    # L + 10-bp gaps run 0 .. 3 L and 0 .. 5 (L + 10); 2 L + 10 bp and 600 bp have one candidate length, below and above 512) and
+    # both workgroup sizes of fig_pack.h's class table (2 L + 10 <= 448 columns: 256 threads; the others 512).  The clipped reads
+    # are kept to <= 104 bases inside the gap, where the reference's partial_left[100] / partial_right[100] are in bounds.
+    "partial_L150": dict(seed=1050, mode="partial", gap_specs=[(1500, 50), (2800, 160), (4200, 310), (5800, 600)], read_len=150, insert_mean=340,
+                         insert_sd=10, coverage=5, err=0.005, n_model_pairs=400, contig_len=7900),
+    "partial_L199": dict(seed=1099, mode="partial", gap_specs=[(1500, 209), (3000, 408), (4700, 600)], read_len=199, insert_mean=438,
+                         insert_sd=10, coverage=10, err=0.005, n_model_pairs=400, contig_len=6800),
+    # unmapped mode: L % 4 == 3 (the shared-factor chain's one-base tail, fig_engine_shared.h) and L < 32 (no shared-factor form)
+    "unmapped_L75": dict(seed=975, mode="unmapped", gap_specs=[(1500, 12), (2900, 600)], read_len=75, insert_mean=600, insert_sd=30, coverage=8,
+                         err=0.005, n_model_pairs=400, contig_len=5000),
+    "unmapped_L31": dict(seed=931, mode="unmapped", gap_specs=[(1500, 12), (2900, 29), (4300, 600)], read_len=31, insert_mean=600, insert_sd=30,
+                         coverage=8, err=0.005, n_model_pairs=400, contig_len=6400),
 }
 N_THREADS = {"threads3": 3, "ot_carry_t3": 3}
 SET_INPUTMEAN = {"inputmean": 1}
@@ -153,7 +167,13 @@ def _post_inputmean(case):
     case.n_pairs = len(case.myout) // 2
 
 
-POST = {"ot_carry": _post_ot_carry, "ot_carry_t3": _post_ot_carry, "inputmean": _post_inputmean, "threads3": _post_threads3, "edge_no_reads": _post_edge_no_reads, "repeat_flanks": _post_repeat_flanks, "cap_3001": _post_cap_3001, "stat2_hint": _post_stat2_hint}
+def _post_clip_hang(case):
+    from tools.fuzz_ref import clip_hang, ref_defined
+    clip_hang(case)
+    assert ref_defined(case) and all(len(g.partial) >= 3 for g in case.gaps)
+
+
+POST = {"partial_L150": _post_clip_hang, "partial_L199": _post_clip_hang, "ot_carry": _post_ot_carry, "ot_carry_t3": _post_ot_carry, "inputmean": _post_inputmean, "threads3": _post_threads3, "edge_no_reads": _post_edge_no_reads, "repeat_flanks": _post_repeat_flanks, "cap_3001": _post_cap_3001, "stat2_hint": _post_stat2_hint}
 
 
 def make(name):
