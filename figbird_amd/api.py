@@ -57,6 +57,14 @@ class FigGapResults(C.Structure):
     ]
 
 
+class FigGapSupport(C.Structure):
+    _fields_ = [("counts", c_i32_p), ("origin", c_i32_p)]
+
+
+# fig_gap_support::origin (include/figbird_hip.h)
+SUP_NONE, SUP_FINAL, SUP_ORIGINAL, SUP_TIEBREAK = 0, 1, 2, 4
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -65,7 +73,7 @@ class FigStats(C.Structure):
 
 
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
-           "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_batch_free", "fig_fill_gaps",
+           "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
            "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset"]
 
 _lib = None
@@ -98,6 +106,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.fig_get_stats.argtypes = [C.c_void_p, C.POINTER(FigStats)]
     lib.fig_batch_probe_reach.argtypes = [C.c_void_p, c_u8_p]
     lib.fig_batch_set_ot_preset.argtypes = [C.c_void_p, c_u8_p]
+    if hasattr(lib, "fig_fill_resident_ex"):          # (the CPU emulation of the tests implements the ABI without it)
+        lib.fig_fill_resident_ex.argtypes = [C.c_void_p, C.POINTER(FigGapResults), C.POINTER(FigGapSupport)]
     if path is None:
         _lib = lib
     return lib
@@ -121,6 +131,7 @@ def load_host_library() -> C.CDLL:
         _host.fighost_run_shard.argtypes = [C.c_void_p, c_i64_p, C.c_int64, C.POINTER(FigGapBatch), c_i64_p, c_i64_p]
         _host.fighost_run_ot_presets.argtypes = [C.c_void_p, c_u8_p, c_u8_p]
         _host.fighost_run_write.argtypes = [C.c_void_p, c_i32_p, c_i32_p, c_i64_p, C.c_char_p, c_i32_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
+        _host.fighost_run_write_support.argtypes = [C.c_void_p, c_i32_p, c_i64_p, C.c_char_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -263,6 +274,8 @@ class FillResult:
     str_off: Optional[np.ndarray] = None   # int64[n+1]: gap g's string is raw[str_off[g]:str_off[g+1]]
     raw: Optional[np.ndarray] = None       # uint8: all gap strings back to back, as the C ABI wrote them
     draw: Optional[tuple] = None           # (draw_pos, draw_isz, draw_len) planes of fig_gap_results, when requested
+    support: Optional[np.ndarray] = None   # int32 [total, 5]: read counts (A, C, G, T, other) behind raw[i], i.e. base x of gap g at str_off[g] + x
+    support_origin: Optional[np.ndarray] = None   # int32 [n_gaps]: SUP_* mask (fig_gap_support::origin)
 
     @property
     def filled_bases(self) -> int:
@@ -309,7 +322,20 @@ class Engine:
         self.cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(self._cb)))
         self._check(self.lib.fig_batch_upload(self.ctx, C.byref(self._cb)), "fig_batch_upload")
 
-    def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0) -> FillResult:
+    def _fill_resident_call(self, r: "FigGapResults", n: int, cap: int, support: bool):
+        """fig_fill_resident, or fig_fill_resident_ex with a support plane sized for `cap` string bytes; returns
+        (counts [cap, 5], origin [n]) or (None, None)."""
+        if not support:
+            self._check(self.lib.fig_fill_resident(self.ctx, C.byref(r)), "fig_fill_resident")
+            return None, None
+        if not hasattr(self.lib, "fig_fill_resident_ex"):
+            raise RuntimeError("support=True needs fig_fill_resident_ex, which this library does not export")
+        sc = np.zeros((max(cap, 1), 5), dtype=np.int32); so = np.zeros(max(n, 1), dtype=np.int32)
+        s = FigGapSupport(); s.counts = _p(sc, c_i32_p); s.origin = _p(so, c_i32_p)
+        self._check(self.lib.fig_fill_resident_ex(self.ctx, C.byref(r), C.byref(s)), "fig_fill_resident_ex")
+        return sc, so
+
+    def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False) -> FillResult:
         n = self.n_gaps
         fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
         so = np.zeros(n + 1, dtype=np.int64); st = np.zeros(max(self.cap, 1), dtype=np.uint8)
@@ -327,7 +353,12 @@ class Engine:
             if plane_reads > 0:
                 pr = np.zeros((max(n, 1), debug_cand, plane_reads))
                 r.dbg_plane_reads = plane_reads; r.dbg_read_maxlv = _p(pr, c_double_p)
-        self._check(self.lib.fig_fill_resident(self.ctx, C.byref(r)), "fig_fill_resident")
+        if draw:
+            nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1])
+            dpos = np.full(max(nr, 1), np.iinfo(np.int32).min, dtype=np.int32); disz = np.zeros(max(nr, 1), dtype=np.int32)
+            dlen = np.full(max(2 * n, 1), -1, dtype=np.int32)
+            r.draw_pos = _p(dpos, c_i32_p); r.draw_isz = _p(disz, c_i32_p); r.draw_len = _p(dlen, c_i32_p)
+        sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
         raw = st.tobytes()
         strings = [raw[so[g]:so[g + 1]].decode() for g in range(n)]
         cand = None
@@ -343,6 +374,10 @@ class Engine:
             res.counts = pc[:n]
         if debug_cand > 0 and plane_reads > 0:
             res.read_maxlv = pr[:n]
+        if draw:
+            res.draw = (dpos[:nr], disz[:nr], dlen[:2 * n])
+        if support:
+            res.support = sup_c[:int(so[n])]; res.support_origin = sup_o[:n]
         return res
 
     def free_batch(self):
@@ -371,10 +406,11 @@ class Engine:
         if self.n_gaps > 0:
             self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
 
-    def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False) -> FillResult:
+    def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
-        resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free)."""
+        resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
+        read support as well (fields `support`, `support_origin`)."""
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
@@ -387,21 +423,30 @@ class Engine:
         dlen = np.full(max(2 * n, 1), -1, dtype=np.int32)
         if draw:
             r.draw_pos = _p(dpos, c_i32_p); r.draw_isz = _p(disz, c_i32_p); r.draw_len = _p(dlen, c_i32_p)
+        sup_c = sup_o = None
+        if support and not hasattr(self.lib, "fig_fill_resident_ex"):
+            raise RuntimeError("support=True needs fig_fill_resident_ex, which this library does not export")
+        if n > 0 and not resident and support:            # (fig_fill_gaps has no support argument: upload, then the resident call)
+            self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
+            resident = True
         if n > 0 and resident:
             try:
-                self._check(self.lib.fig_fill_resident(self.ctx, C.byref(r)), "fig_fill_resident")
+                sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
             finally:
                 self.lib.fig_batch_free(self.ctx)
         elif n > 0:
             self._check(self.lib.fig_fill_gaps(self.ctx, C.byref(cbatch), C.byref(r)), "fig_fill_gaps")
         res = FillResult(fl[:n].copy(), gt[:n].copy(), None, None, str_off=so, raw=st)
         res.draw = (dpos[:nr], disz[:nr], dlen[:2 * n])
+        if support:
+            res.support = sup_c[:int(so[n])] if sup_c is not None else np.zeros((0, 5), dtype=np.int32)
+            res.support_origin = sup_o[:n] if sup_o is not None else np.zeros(0, dtype=np.int32)
         return res
 
-    def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0) -> FillResult:
+    def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw)
         finally:
             self.free_batch()
 

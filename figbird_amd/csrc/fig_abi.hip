@@ -599,9 +599,12 @@ static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln, 
     return nl;
 }
 
-extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
+extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) { return fig_fill_resident_ex(ctx, out, nullptr); }
+
+extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fig_gap_support *sup) {
     if (!ctx || !out || !ctx->have_batch) return FIG_EINVAL;
     if (!out->filled_len || !out->gaptofill || !out->str_off || (!out->str && ctx->str_total > 0)) return FIG_EINVAL;
+    if (sup && (!sup->counts || !sup->origin)) return FIG_EINVAL;
     hipSetDevice(ctx->device);
     int64_t ng = ctx->n_gaps;
     FigDevBatch &db = ctx->db;
@@ -635,6 +638,13 @@ extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
         if (talloc((size_t)nr * 4, &p)) { tfree(); return FIG_ENOMEM; } db.draw_isz = (int32_t *)p;
         if (talloc((size_t)ng * 8, &p)) { tfree(); return FIG_ENOMEM; } db.draw_len = (int32_t *)p;
         hipMemsetAsync(db.draw_isz, 0, (size_t)nr * 4, ctx->stream);
+    }
+    const size_t sup_n = (size_t)ctx->str_total * 5;
+    if (sup) {                        // per-base read support: one slot per string slot, zero unless fig_gap_end writes it
+        if (talloc(sup_n * 4, &p)) { tfree(); return FIG_ENOMEM; } db.sup_counts = (int32_t *)p;
+        if (talloc((size_t)ng * 4, &p)) { tfree(); return FIG_ENOMEM; } db.sup_origin = (int32_t *)p;
+        hipMemsetAsync(db.sup_counts, 0, sup_n * 4, ctx->stream);
+        hipMemsetAsync(db.sup_origin, 0, (size_t)ng * 4, ctx->stream);
     }
     hipMemsetAsync(db.counters, 0, 512, ctx->stream);
     // a previous call that failed half-way may have left queue heads / ping-pong selectors inconsistent: start clean
@@ -701,6 +711,11 @@ extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
         hipMemcpyAsync(out->draw_isz, db.draw_isz, (size_t)nr * 4, hipMemcpyDeviceToHost, ctx->stream);
         hipMemcpyAsync(out->draw_len, db.draw_len, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream);
     }
+    std::vector<int32_t> hsup(sup ? sup_n : 0);
+    if (sup) {
+        if (sup_n) hipMemcpyAsync(hsup.data(), db.sup_counts, sup_n * 4, hipMemcpyDeviceToHost, ctx->stream);
+        hipMemcpyAsync(sup->origin, db.sup_origin, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
+    }
     hipEventRecord(ctx->ev1, ctx->stream);
     e = hipStreamSynchronize(ctx->stream);
     tfree();
@@ -721,7 +736,9 @@ extern "C" int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out) {
     ctx->stats.spec_flops = (double)cnt[2];
     ctx->stats.mle_alg_flops = (double)cnt[3];
     ctx->stats.mle_exec_flops = (double)cnt[4];
-    return fig_compact_results(ng, hstr.data(), ctx->h_str_off.data(), out);
+    int rc = fig_compact_results(ng, hstr.data(), ctx->h_str_off.data(), out);
+    if (!rc && sup) fig_compact_support(ng, hsup.data(), ctx->h_str_off.data(), out, sup->counts);
+    return rc;
 }
 
 extern "C" int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) { return fig_fill_gaps_once(ctx, batch, out); }

@@ -14,6 +14,9 @@
 #include "fig_gaprules.h"
 // (fig_engine.h and fig_pack.h must already be included: FigKernArgs, FigLaunchClass and fig_model_fmm come from them)
 
+static_assert(FIG_ORG_NONE == FIG_SUP_NONE && FIG_ORG_FINAL == FIG_SUP_FINAL && FIG_ORG_ORIGINAL == FIG_SUP_ORIGINAL && FIG_ORG_TIEBREAK == FIG_SUP_TIEBREAK,
+              "the engine's path mask (fig_types.h) is fig_gap_support::origin");
+
 static inline const char *fig_strerror_text(int code) {
     switch (code) {
         case FIG_OK: return "ok";
@@ -92,6 +95,7 @@ static inline void fig_batch_clear_planes(FigDevBatch &db) {
     db.dbg_n_cand = nullptr; db.dbg_cand_i = nullptr; db.dbg_cand_lik = nullptr; db.dbg_max_cand = 0; db.dbg_n_place = nullptr;
     db.draw_pos = db.draw_isz = db.draw_len = nullptr;
     db.dbg_counts = db.dbg_read_maxlv = nullptr; db.dbg_plane_cols = db.dbg_plane_reads = 0;
+    db.sup_counts = db.sup_origin = nullptr;
 }
 
 // the launch arguments of a class (FigKernArgs, fig_engine.h)
@@ -130,6 +134,15 @@ static int fig_compact_results(int64_t ng, const char *src, const int64_t *src_o
     }
     out->str_off[ng] = o;
     return FIG_OK;
+}
+
+// The support plane travels with the strings: five int32 per string byte, from the slot at src_off[g] * 5 to
+// out->str_off[g] * 5 (after fig_compact_results has set out->str_off).
+static void fig_compact_support(int64_t ng, const int32_t *src, const int64_t *src_off, const fig_gap_results *out, int32_t *dst) {
+    for (int64_t g = 0; g < ng; g++) {
+        int n = out->filled_len[g];
+        if (n > 0) memcpy(dst + out->str_off[g] * 5, src + src_off[g] * 5, (size_t)n * 5 * sizeof(int32_t));
+    }
 }
 
 // fig_fill_gaps: upload + fill + free, on the public calls

@@ -171,8 +171,8 @@ struct FigState {
     int fin_i[8];                    // finalize statistics (flags / max / counts), filled with atomics
     FigLoop L;
     // useful-work counters of this gap (speculative candidates that are discarded never reach them)
-    unsigned long long flops_useful; int n_place, pad_np;
-    int dbg_j, pad_dj;               // candidate index whose numeric planes are being exported (-1: none)
+    unsigned long long flops_useful; int n_place, sup_any;   // sup_any: fig_gap_end's "some count of the support plane is nonzero" (many lanes store 1 between two barriers)
+    int dbg_j, sup_origin;           // candidate index whose numeric planes are being exported (-1: none) ; FIG_ORG_* path of the gap's last finalize (support plane only)
 };
 
 struct FigTrip { int v[3]; };

@@ -1101,6 +1101,7 @@ FIG_D void fig_finalize(FigEng &E, int gl) {
     int left_start_zero = 0, right_fin_glen = 0, totalCount = 0, discardedCount = 0;
     int unmapped_max_left = 0, unmapped_max_right = 0, leftcount = 0, rightcount = 0;
     int draw_on = E.B->draw_pos != nullptr;
+    int sup = FIG_ORG_FINAL;           // lane 0: where the counts behind the emitted string come from (fig_gap_support::origin)
 
     if (M.unmapped) {
         if (E.tid == 0) { if (E.B->draw_len) E.B->draw_len[(long long)E.g->gapNo * 2] = G; for (int q = 0; q < 8; q++) S.fin_i[q] = 0; }
@@ -1219,6 +1220,7 @@ FIG_D void fig_finalize(FigEng &E, int gl) {
                 S.G = G0; fig_ise(E);
                 int offset = S.G > gl ? 0 : (gl - S.G);
                 fig_clear_counts(E, S.G + offset);
+                sup = FIG_ORG_NONE;
                 int do_rc = 0;
                 if (!S.ctl[2] && S.ctl[3] && S.ctl[5] >= st) do_rc = 1;
                 else if (S.ctl[2] && !S.ctl[3] && S.ctl[4] >= st) do_rc = 1;
@@ -1232,7 +1234,7 @@ FIG_D void fig_finalize(FigEng &E, int gl) {
                                 if (pos + j >= 0 && pos + j < S.G) E.scr.cnt[fig_read_code(E.B->packed, woff, len, j) * cg + pos + j] += 1;
                         }
                     }
-                    recompute_flag = 1;
+                    recompute_flag = 1; sup = FIG_ORG_ORIGINAL;
                 }
             }
         }
@@ -1254,6 +1256,7 @@ FIG_D void fig_finalize(FigEng &E, int gl) {
                 S.G = G0; fig_ise(E);
                 int offset = S.G > gl ? 0 : (gl - S.G);
                 fig_clear_counts(E, S.G + offset);
+                sup = FIG_ORG_NONE;
                 if (used_read < 2 || gap_case == 4) u_flag = 0;
                 else {
                     // recompute1(partial_read_pos_arr_org), :4875-4906
@@ -1269,10 +1272,12 @@ FIG_D void fig_finalize(FigEng &E, int gl) {
                     }
                     for (int i = 0; i < S.partial_read_count; i++) for (int q = 0; q < 3; q++) E.scr.prf[i * 3 + q] = E.scr.ppos_org[i * 3 + q];
                     fig_detect_overlap(E, E.scr.prf, 3, S.G, ret_val, 8);
-                    if (ret_val[1] == -1) { fig_clear_counts(E, S.G + offset); u_flag = 0; }
+                    sup = FIG_ORG_ORIGINAL;
+                    if (ret_val[1] == -1) { fig_clear_counts(E, S.G + offset); u_flag = 0; sup = FIG_ORG_NONE; }
                 }
             }
             if (u_flag == 1 && ret_val[0] == 0 && ret_val[1] == 0) {
+                if (sup != FIG_ORG_NONE) sup |= FIG_ORG_TIEBREAK;
                 for (int j = 0; j < S.G; j++) {
                     int nz = 0;
                     for (int k = 0; k < 4; k++) if (E.scr.cnt[k * cg + j] > 0) nz++;
@@ -1300,11 +1305,13 @@ FIG_D void fig_finalize(FigEng &E, int gl) {
                 S.G = G0; fig_ise(E);
                 int offset = S.G > gl ? 0 : (gl - S.G);
                 fig_clear_counts(E, S.G + offset);
+                sup = FIG_ORG_NONE;
             }
         }
         FIG_SYNC();
         if (S.bc_i == 1) fig_compute_sequence(E, 1, 0);
     }
+    if (E.tid == 0 && E.B->sup_counts) S.sup_origin = sup;
     FIG_SYNC();
 }
 

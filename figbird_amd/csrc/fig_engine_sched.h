@@ -33,7 +33,7 @@ FIG_D void fig_gap_begin(FigEng &E) {
         // the oracle and the engine take 0, i.e. the run(originalGap) + finalize(originalGap) branch
         E.scr.used_read_arr[0] = 0;
         S.best_len = S.cur_len = S.prev_len = S.orig_len = 0;
-        S.flops_useful = 0; S.n_place = 0; S.dbg_j = -1; S.pad_dj = 0;
+        S.flops_useful = 0; S.n_place = 0; S.dbg_j = -1; S.sup_origin = FIG_ORG_NONE;
         fig_flank_tables(E);
         if (E.B->dbg_n_cand) E.B->dbg_n_cand[g.gapNo] = 0;
         if (E.B->draw_len) { E.B->draw_len[(long long)g.gapNo * 2] = -1; E.B->draw_len[(long long)g.gapNo * 2 + 1] = -1; }
@@ -276,6 +276,24 @@ FIG_D void fig_gap_end(FigEng &E) {
     for (int x = E.tid; x < len && x < g.alloc_arg; x += E.nt) {
         int c = x < S.cons_len ? E.scr.cons[x] : 4;
         dst[x] = A[c > 4 ? 4 : c];
+    }
+    if (E.B->sup_counts) {
+        // per-base read support: the countsGap columns finalize's last computeSequence(1,0) called the string from (integer-valued
+        // doubles).  A string that is not such a call (no finalize at all, or counts cleared with nothing put back) has none,
+        // and a path that left no count at all (nothing recorded to restore, every column given up by the tie-break) is NONE too.
+        const int org = S.sup_origin, cg = E.capG;
+        int32_t *sup = E.B->sup_counts + g.strOff * 5;
+        if (E.tid == 0) S.sup_any = 0;
+        FIG_SYNC();
+        int any = 0;
+        for (int i = E.tid; i < 5 * len && i < 5 * g.alloc_arg; i += E.nt) {
+            const int x = i / 5, b = i - 5 * x;
+            const int32_t v = (org != FIG_ORG_NONE && x < S.cons_len && x < cg) ? (int32_t)E.scr.cnt[b * cg + x] : 0;
+            sup[i] = v; any |= v;
+        }
+        if (any) S.sup_any = 1;
+        FIG_SYNC();
+        if (E.tid == 0) E.B->sup_origin[g.gapNo] = S.sup_any ? org : FIG_ORG_NONE;
     }
     if (E.tid == 0) {
         E.B->filled_len[g.gapNo] = len; E.B->gaptofill[g.gapNo] = S.gaptofill;

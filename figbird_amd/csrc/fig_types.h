@@ -22,6 +22,9 @@
 // packed-consensus record per column, the per-wave factor buffers, the packed consensus words (kc, kn) and slack
 #define FIG_TILED_MLE_DOUBLES(ncolE, nw) (7LL * (ncolE) + (long long)(nw) * FIG_MLE_FB + ((ncolE) + 15) / 16 + 16 + 8)
 
+// Path mask of a gap's support plane (FigDevBatch::sup_origin); the values of the public FIG_SUP_* (fig_abi_host.h asserts it)
+enum { FIG_ORG_NONE = 0, FIG_ORG_FINAL = 1, FIG_ORG_ORIGINAL = 2, FIG_ORG_TIEBREAK = 4 };
+
 struct FigDevModel {
     int32_t L;                       // maxReadLength
     int32_t Tmin, Tmax, cutoff;      // insertThresholdMin/Max, gapProbCutOff
@@ -85,6 +88,9 @@ struct FigDevBatch {
     uint8_t *persist;                // per-gap persistent slabs
     int32_t *gapctl;                 // [n_gaps*4] {status (0 finished, 1 more candidates, 2 loop done), next j, range, reach bit of fig_probe_kernel}
     const uint8_t *ot_preset;        // [n_gaps] 1 = the gap's worker process has set overlap_threshold before it gets to the gap (Figbird.cpp:103, :6317)
+    // optional per-base read support (fig_gap_support): the countsGap columns behind the emitted string, [(strOff + x) * 5 + b],
+    // and the FIG_ORG_* path mask per gap; both null = off (fig_gap_end takes one uniform branch and stores nothing)
+    int32_t *sup_counts, *sup_origin;
 };
 
 #endif

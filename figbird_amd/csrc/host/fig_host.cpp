@@ -728,6 +728,27 @@ bool write_gapout(const RunArgs &a, const Batch &b, const Results &r, std::strin
     return true;
 }
 
+bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+    FILE *f = fopen((a.tmp + "gapsupport.txt").c_str(), "w");
+    if (!f) { err = "can't write gapsupport.txt"; return false; }
+    std::string S, D;
+    for (size_t g = 0; g < b.gap_contig.size(); g++) {
+        const int n = r.filled_len[g] > 0 ? r.filled_len[g] : 0;
+        S.clear(); D.clear();
+        for (int x = 0; x < n; x++) {
+            const int32_t *c = &r.sup_counts[(size_t)(r.str_off[g] + x) * 5];
+            const char ch = r.str[(size_t)r.str_off[g] + x];
+            const int k = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1;
+            if (x) { S += ','; D += ','; }
+            S += std::to_string(k >= 0 ? c[k] : 0);
+            D += std::to_string((long long)c[0] + c[1] + c[2] + c[3] + c[4]);
+        }
+        fprintf(f, "%d\t%d\t%ld\t%d\t%d\t%d\t%s\t%s\n", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g], n, r.sup_origin[g], S.c_str(), D.c_str());
+    }
+    fclose(f);
+    return true;
+}
+
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     FILE *f = fopen((a.tmp + "draw.txt").c_str(), "w");
     if (!f) { err = "can't write draw.txt"; return false; }
@@ -1008,5 +1029,21 @@ extern "C" int fighost_run_write(void *h, const int32_t *filled_len, const int32
         !fighost::write_scaffold(r->a, r->sc, r->B, R, e)) {
         set_err(err, errcap, e); return -1;
     }
+    return 0;
+}
+
+// gapsupport.txt of the WHOLE gap set (FIGFILL_SUPPORT=1): sup_counts [str_off[n_gaps]*5] indexed like str, sup_origin [n_gaps]
+extern "C" int fighost_run_write_support(void *h, const int32_t *filled_len, const int64_t *str_off, const char *str,
+                                         const int32_t *sup_counts, const int32_t *sup_origin, char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size();
+    fighost::Results R;
+    R.filled_len.assign(filled_len, filled_len + ng);
+    R.str_off.assign(str_off, str_off + ng + 1);
+    R.str.assign(str, str + (size_t)str_off[ng]);
+    R.sup_counts.assign(sup_counts, sup_counts + (size_t)str_off[ng] * 5);
+    R.sup_origin.assign(sup_origin, sup_origin + ng);
+    std::string e;
+    if (!fighost::write_support(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
     return 0;
 }

@@ -86,11 +86,16 @@ struct Results {
     std::vector<int32_t> filled_len, gaptofill, draw_pos, draw_isz, draw_len;
     std::vector<int64_t> str_off;
     std::string str;
+    // per-base read support (fig_gap_support), when asked for: [str.size()*5] indexed like str, and [n_gaps]
+    std::vector<int32_t> sup_counts, sup_origin;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
 bool write_gapout(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gapsupport.txt (no counterpart in the reference): per gap `g contig start G0 n origin S D`, tab-separated, S = n
+// comma-separated supports of the called base (0 under an N), D = n comma-separated depths (sum of the five counts)
+bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // filledContigs.fa + Ncount.txt (FillGaps.cpp:708-926)
 bool write_scaffold(const RunArgs &a, const Scaffold &sc, const Batch &b, const Results &r, std::string &err);
 

@@ -19,6 +19,22 @@
 
 using namespace fighost;
 
+// fig_fill_resident_ex is the one call of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests
+// implements the calls it was written against): bound weakly, and asking for the support plane without it is an error.
+extern "C" int fig_fill_resident_ex(fig_ctx *, fig_gap_results *, const fig_gap_support *) __attribute__((weak));
+
+// FIGFILL_SUPPORT=1: also ask for the per-base read support and write <tmp>/gapsupport.txt
+static bool want_support() { const char *s = getenv("FIGFILL_SUPPORT"); return s && atoi(s) == 1; }
+
+// the fill, with R.sup_counts / R.sup_origin sized and filled when `support`
+static int fill_resident(fig_ctx *ctx, fig_gap_results *fr, Results &R, int64_t ng, bool support) {
+    if (!support) return fig_fill_resident(ctx, fr);
+    if (!fig_fill_resident_ex) { fprintf(stderr, "figfill: FIGFILL_SUPPORT=1 needs fig_fill_resident_ex, which the library behind this build does not export\n"); return FIG_EUNSUP; }
+    R.sup_counts.assign((size_t)std::max<int64_t>(fr->str_capacity, 1) * 5, 0); R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    fig_gap_support fs; fs.counts = R.sup_counts.data(); fs.origin = R.sup_origin.data();
+    return fig_fill_resident_ex(ctx, fr, &fs);
+}
+
 static int fail(const std::string &m) { fprintf(stderr, "%s\n", m.c_str()); return 1; }
 
 // ---- N GPUs of one node from this process (FIGFILL_DEVICES=0,1,...; the reference starts its own workers too,
@@ -63,7 +79,7 @@ static void shard_fill(int device, const fig_model *fm, const Scaffold *sc, Shar
     fr.filled_len = R.filled_len.data(); fr.gaptofill = R.gaptofill.data(); fr.str_off = R.str_off.data();
     fr.str = &R.str[0]; fr.str_capacity = (int64_t)R.str.size();
     fr.draw_pos = R.draw_pos.data(); fr.draw_isz = R.draw_isz.data(); fr.draw_len = R.draw_len.data();
-    rc = fig_fill_resident(S->ctx, &fr);
+    rc = fill_resident(S->ctx, &fr, R, ng, want_support());
     fig_get_stats(S->ctx, &S->st);
     if (rc) return shard_fail(S, rc, std::string("fig_fill_resident on device ") + std::to_string(device));
     fig_ctx_destroy(S->ctx); S->ctx = nullptr;
@@ -107,11 +123,17 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         st.n_launches += runs[r].st.n_launches;
     }
     R.str.clear();
+    const bool support = want_support();
+    if (support) R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
     for (int64_t g = 0; g < ng; g++) {
         const ShardRun &S = runs[owner[g]]; const int64_t k = local[g];
         R.filled_len[g] = S.R.filled_len[k]; R.gaptofill[g] = S.R.gaptofill[k];
         R.str_off[g] = (int64_t)R.str.size();
         R.str.append(S.R.str, (size_t)S.R.str_off[k], (size_t)(S.R.str_off[k + 1] - S.R.str_off[k]));
+        if (support) {                                    // the plane travels with the string: five counts per byte
+            R.sup_counts.insert(R.sup_counts.end(), S.R.sup_counts.begin() + S.R.str_off[k] * 5, S.R.sup_counts.begin() + S.R.str_off[k + 1] * 5);
+            R.sup_origin[g] = S.R.sup_origin[k];
+        }
         R.draw_len[2 * g] = S.R.draw_len[2 * k]; R.draw_len[2 * g + 1] = S.R.draw_len[2 * k + 1];
         const int64_t nu = B.u_read_off[g + 1] - B.u_read_off[g], np = B.p_read_off[g + 1] - B.p_read_off[g];
         const int64_t snu = (int64_t)S.sub.u_anchor_pos.size();
@@ -120,6 +142,7 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
     }
     R.str_off[ng] = (int64_t)R.str.size();
     if (R.str.empty()) R.str.assign(1, 'N');
+    if (support && R.sup_counts.empty()) R.sup_counts.assign(5, 0);
     return 0;
 }
 
@@ -191,6 +214,7 @@ int main(int argc, char **argv) {
         if (!write_draw(a, B, R, err)) return fail(err);
         if (!write_gaploads(a, B, err)) return fail(err);
         if (!write_scaffold(a, sc, B, R, err)) return fail(err);
+        if (want_support() && !write_support(a, B, R, err)) return fail(err);
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         printf("Time taken = %g seconds (%zu GPUs; slowest shard's device kernels %.3f ms, %lld placeReads calls)\n", secs, devices.size(), st.kernel_ms, (long long)st.place_calls);
         printf("======================================\n");
@@ -231,7 +255,7 @@ int main(int argc, char **argv) {
         rc = fig_batch_probe_reach(ctx, reach.data());
         if (!rc) { ot_presets_from_reach(B, reach.data()); rc = fig_batch_set_ot_preset(ctx, B.gap_ot_preset.data()); }
     }
-    if (!rc) rc = fig_fill_resident(ctx, &fr);
+    if (!rc) rc = fill_resident(ctx, &fr, R, ng, want_support());
     fig_stats st; memset(&st, 0, sizeof(st)); fig_get_stats(ctx, &st);
     fig_ctx_destroy(ctx);
     if (rc) return fail(std::string("figfill: fill: ") + fig_strerror(rc));
@@ -240,6 +264,7 @@ int main(int argc, char **argv) {
     if (!write_draw(a, B, R, err)) return fail(err);
     if (!write_gaploads(a, B, err)) return fail(err);
     if (!write_scaffold(a, sc, B, R, err)) return fail(err);
+    if (want_support() && !write_support(a, B, R, err)) return fail(err);
     if (trace) {
         FILE *f = fopen(trace, "w");
         if (f) {

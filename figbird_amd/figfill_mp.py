@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import sys
 import time
 
@@ -32,6 +33,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0")) if device_index is None else device_index
     t0 = time.time()
+    # FIGFILL_SUPPORT=1: also gapsupport.txt, the per-base read support (fig_gap_support); read as figfill reads it, atoi(s) == 1
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_SUPPORT", ""))
+    support = m is not None and int(m.group(0)) == 1
     own_pg = False
     if world > 1 and not dist.is_initialized():
         be = backend or ("nccl" if torch.cuda.is_available() else "gloo")
@@ -95,7 +99,7 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
             preset = np.zeros(max(n, 1), dtype=np.uint8)
             host.fighost_run_ot_presets(h, api._p(reach, api.c_u8_p), api._p(preset, api.c_u8_p))
             eng.set_ot_preset(preset[mine] if len(mine) else np.zeros(0, dtype=np.uint8))
-            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True)
+            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support)
             st = eng.stats()
             eng.close()
         except Exception as e:
@@ -111,7 +115,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
         if fdist.all_status_max(prc, dev) != 0:
             return 1
         dpos, disz, dlen = res.draw
-        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz])
+        # the support plane travels as two more extras: the shard's counts, five per string byte in shard order, and its origins
+        sup_x = [res.support.reshape(-1), res.support_origin] if support else []
+        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz] + sup_x)
         wrc = 0
         try:
             fl, gt, ps, per_rank = out
@@ -121,10 +127,17 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 NU, NP = int(uo[-1]), int(po[-1])
                 g_pos = np.full(max(NU + NP, 1), np.iinfo(np.int32).min, dtype=np.int32); g_isz = np.zeros(max(NU + NP, 1), dtype=np.int32)
                 g_len = np.full(max(2 * n, 1), -1, dtype=np.int32)
-                for ids, r_len, r_pos, r_isz in per_rank:
+                g_sup = np.zeros((max(int(ps.off[-1]), 1), 5), dtype=np.int32); g_org = np.zeros(max(n, 1), dtype=np.int32)
+                for ids, r_len, r_pos, r_isz, *r_sup in per_rank:
                     ids = np.asarray(ids, dtype=np.int64)
                     if len(ids) == 0:
                         continue
+                    if support:      # a shard's strings lie back to back in its own gap order; ps.off is the global layout
+                        ln = np.maximum(fl[ids], 0).astype(np.int64)
+                        src0 = np.cumsum(ln) - ln
+                        idx = np.repeat(ps.off[ids] - src0, ln) + np.arange(int(ln.sum()), dtype=np.int64)
+                        g_sup[idx] = r_sup[0].reshape(-1, 5)[:int(ln.sum())]
+                        g_org[ids] = r_sup[1]
                     g_len[2 * ids] = r_len[0::2]; g_len[2 * ids + 1] = r_len[1::2]
                     cu = nu[ids]; cp = npp[ids]
                     su_ = int(cu.sum())
@@ -139,6 +152,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 wrc = host.fighost_run_write(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(gt if n else np.zeros(1, np.int32), api.c_i32_p),
                                              api._p(ps.off, api.c_i64_p), C.cast(raw.ctypes.data, C.c_char_p),
                                              api._p(g_pos, api.c_i32_p), api._p(g_isz, api.c_i32_p), api._p(g_len, api.c_i32_p), err, 512)
+                if wrc == 0 and support:
+                    wrc = host.fighost_run_write_support(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
+                                                         C.cast(raw.ctypes.data, C.c_char_p), api._p(g_sup, api.c_i32_p), api._p(g_org, api.c_i32_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

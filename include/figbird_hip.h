@@ -135,6 +135,22 @@ typedef struct fig_gap_results {
     double *dbg_read_maxlv;             /* [n_gaps*dbg_max_cand*dbg_plane_reads]            */
 } fig_gap_results;
 
+/* Optional per-base read support of a fill (fig_fill_resident_ex): for every byte of results->str the five read counts
+ * (A, C, G, T, other) of the countsGap column the byte was called from -- the columns as the last computeSequence(check=1)
+ * of finalize (Figbird.cpp:4417-4508 called from :4929-5659) consumed them -- and per gap where those counts came from.
+ * Call rule: first strict maximum over the five counts; 'N' when the maximum is 0 or the "other" row wins.  An 'N' over a
+ * column WITH support was masked afterwards (recheck_sequence / findRegion, :4594-4743).  All zero for a gap whose string is
+ * not such a call: never attempted, closed by a negative overlap, or counts cleared with nothing put back (origin NONE). */
+#define FIG_SUP_NONE 0       /* the gap's plane is all zero (and only then)                                            */
+#define FIG_SUP_FINAL 1      /* pile-up of this fill's final placement: the reads draw_pos reports, at those offsets    */
+#define FIG_SUP_ORIGINAL 2   /* restored from the placement at the original gap length (recompute1 / recompute2)        */
+#define FIG_SUP_TIEBREAK 4   /* or'ed in: the partial-mode check_update pass ran over the columns (:5575-5590) -- it adds
+                              * 10 to one of A..T of a column to settle a near-tie by base quality, or zeroes A..T        */
+typedef struct fig_gap_support {
+    int32_t *counts;                    /* [str_capacity*5] compacted exactly like str: base x of gap g is at (str_off[g]+x)*5 */
+    int32_t *origin;                    /* [n_gaps] FIG_SUP_* mask                                                      */
+} fig_gap_support;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -165,6 +181,9 @@ int64_t fig_results_capacity(const fig_model *model, const fig_gap_batch *batch)
  * fig_fill_gaps(ctx, batch, out) == fig_batch_upload + fig_fill_resident + fig_batch_free. */
 int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *batch);
 int fig_fill_resident(fig_ctx *ctx, fig_gap_results *out);
+/* fig_fill_resident that also hands back the per-base read support; sup == NULL is fig_fill_resident itself.  FIG_EINVAL
+ * when sup is given with counts or origin NULL. */
+int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fig_gap_support *sup);
 void fig_batch_free(fig_ctx *ctx);
 int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out);
 
