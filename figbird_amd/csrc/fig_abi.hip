@@ -24,9 +24,8 @@
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
 #define FIG_PROF_BEGIN() const unsigned long long _k0 = __builtin_readcyclecounter()
-#define FIG_PROF_FLUSH() do { if (E.lane == 0) { atomicAdd(&B.counters[30], E.wait_cycles); atomicAdd(&B.counters[31], (unsigned long long)__builtin_readcyclecounter() - _k0); \
-    for (int i = 0; i < 22; i++) if (E.prof[i]) atomicAdd(&B.counters[8 + i], E.prof[i]); \
-    for (int i = 22; i < 40; i++) if (E.prof[i]) atomicAdd(&B.counters[32 + (i - 22)], E.prof[i]); } } while (0)
+#define FIG_PROF_FLUSH() do { if (E.lane == 0) { atomicAdd(&B.counters[FIG_CNT_WAIT], E.wait_cycles); atomicAdd(&B.counters[FIG_CNT_WAVE], (unsigned long long)__builtin_readcyclecounter() - _k0); \
+    for (int i = 0; i < FIG_PROF_SLOTS; i++) if (E.prof[i]) atomicAdd(&B.counters[i < FIG_PROF_SPLIT ? FIG_CNT_PROF_LO + i : FIG_CNT_PROF_HI + (i - FIG_PROF_SPLIT)], E.prof[i]); } } while (0)
 #else
 #define FIG_PROF_BEGIN() ((void)0)
 #define FIG_PROF_FLUSH() ((void)0)
@@ -34,19 +33,14 @@
 
 // What depends on the launch (thread identity, the workgroup's slab); the LDS / slab layout is fig_eng_carve (fig_engine.h).
 FIG_D void fig_eng_init(FigEng &E, const FigDevModel &M, const FigDevBatch &B, const FigKernArgs &A, bool lds_tab, FigScr &work) {
-    E.tid = threadIdx.x; E.nt = blockDim.x;
-    E.lane = threadIdx.x & 63; E.wave = threadIdx.x >> 6; E.nw = (blockDim.x + 63) >> 6; E.wsz = 64;
+    fig_eng_ident(E, threadIdx.x, blockDim.x, 64);
     E.M = &M; E.B = &B;
     E.flops = 0; E.mle_alg = 0; E.mle_exec = 0; E.wait_cycles = 0;
-    for (int i = 0; i < 40; i++) E.prof[i] = 0;
+    for (int i = 0; i < FIG_PROF_SLOTS; i++) E.prof[i] = 0;
     unsigned char *slab = B.scratch + (long long)blockIdx.x * B.scratch_stride;
     fig_scratch_layout(slab, B.capG, B.capR, B.capP, B.capC, B.capW, B.capE, &work);
     E.scr = work;
     fig_eng_carve(E, M, A, lds_tab);
-}
-
-FIG_D void fig_persist_of(const FigDevBatch &B, const FigDevGap &g, FigPersist &P) {
-    fig_persist_layout(B.persist + g.persistOff, g.capGg, g.nU, g.nP, g.rangeCap, g.nslots, sizeof(FigState), &P);
 }
 
 // Prologue of the five persistent kernels.  Every persistent launch pops from one of its lane's two queue heads and zeroes the
@@ -65,12 +59,27 @@ FIG_D int fig_queue_pop(FigEng &E, const FigDevBatch &B, const FigKernArgs &A) {
     return qi;
 }
 
-// Epilogue: algorithmic flops, and the MLE-pass accounting (raw totals incl. discarded speculation; only their ratio is
-// reported): [3] credited, [4] executed
+// The loop of the persistent kernels: the workgroup pops queue positions until the launch's items are used up and hands each
+// to `body`, one of the work-item functions of fig_engine_sched.h.  `src()` names the items, v[first .. end); it is asked at
+// every pop, which leaves the three values in the kernel arguments instead of in registers that live across the items.
+template <typename T> struct FigItemSrc { const T *v; int first, end; };
+FIG_D FigItemSrc<int32_t> fig_src_order(const FigDevBatch &B, const FigKernArgs &A) { return {B.order, A.q_begin, A.q_end}; }   // the class's gaps, by cost
+
+template <typename Src, typename Body>
+FIG_D void fig_pop_loop(FigEng &E, const FigDevBatch &B, const FigKernArgs &A, Src src, Body body) {
+    while (true) {
+        const int qi = fig_queue_pop(E, B, A);
+        const auto s = src();
+        if (s.first + qi >= s.end) break;
+        body(s.v[s.first + qi]);
+    }
+}
+
+// Epilogue: algorithmic flops and the MLE-pass accounting
 FIG_D void fig_kernel_flush(const FigEng &E, const FigDevBatch &B) {
-    if (E.flops) atomicAdd(&B.counters[1], E.flops);
-    if (E.mle_alg) atomicAdd(&B.counters[3], E.mle_alg);
-    if (E.lane == 0 && E.mle_exec) atomicAdd(&B.counters[4], E.mle_exec);
+    if (E.flops) atomicAdd(&B.counters[FIG_CNT_FLOPS], E.flops);
+    if (E.mle_alg) atomicAdd(&B.counters[FIG_CNT_MLE_ALG], E.mle_alg);
+    if (E.lane == 0 && E.mle_exec) atomicAdd(&B.counters[FIG_CNT_MLE_EXEC], E.mle_exec);
 }
 
 // ---- sequential mode: whole gaps, one workgroup each (FIG_SCHED=seq)
@@ -79,14 +88,7 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_fill_kernel(FigDe
     FigEng E; FigScr work;
     fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     FIG_PROF_BEGIN();
-    while (true) {
-        const int qi = A.q_begin + fig_queue_pop(E, B, A);
-        if (qi >= A.q_end) break;
-        E.g = &B.gaps[B.order[qi]];
-        FigPersist P; fig_persist_of(B, *E.g, P);
-        fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-        fig_fill_gap<LDS_TAB>(E);
-    }
+    fig_pop_loop(E, B, A, [&] { return fig_src_order(B, A); }, [&](int gi) { fig_item_fill<LDS_TAB>(E, work, gi); });
     FIG_PROF_FLUSH();
     fig_kernel_flush(E, B);
 }
@@ -96,81 +98,40 @@ template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_begin_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A) {
     FigEng E; FigScr work;
     fig_kernel_begin(E, M, B, A, LDS_TAB, work);
-    while (true) {
-        const int qi = A.q_begin + fig_queue_pop(E, B, A);
-        if (qi >= A.q_end) break;
-        int gi = B.order[qi];
-        E.g = &B.gaps[gi];
-        FigPersist P; fig_persist_of(B, *E.g, P);
-        fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-        fig_gap_begin<LDS_TAB>(E);
-        if (!E.S->L.inr) {                               // not filled (:6227): one pass without EM, then output
-            while (!E.S->L.done) { fig_eval_candidate<LDS_TAB>(E); fig_loop_step(E); }
-            fig_gap_end<LDS_TAB>(E);
-            if (E.tid == 0) { B.gapctl[gi * 4] = 0; }
-        } else {
-            fig_state_save(E, P);
-            if (E.tid == 0) { B.gapctl[gi * 4] = E.S->L.done ? 2 : 1; B.gapctl[gi * 4 + 1] = E.S->L.j; B.gapctl[gi * 4 + 2] = E.S->L.range; }
-        }
-        __syncthreads();
-    }
+    fig_pop_loop(E, B, A, [&] { return fig_src_order(B, A); }, [&](int gi) { fig_item_begin<LDS_TAB>(E, work, gi); });
     fig_kernel_flush(E, B);
 }
 
-// ---- pre-pass (partial mode): per gap, does its candidate loop get to Figbird.cpp:6317?  -> gapctl[gi*4+3]
+// ---- pre-pass (partial mode): per gap, does its candidate loop get to Figbird.cpp:6317?  -> FigGapCtl::reach
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_probe_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A) {
     FigEng E; FigScr work;
     fig_kernel_begin(E, M, B, A, LDS_TAB, work);
-    while (true) {
-        const int qi = A.q_begin + fig_queue_pop(E, B, A);
-        if (qi >= A.q_end) break;
-        int gi = B.order[qi];
-        E.g = &B.gaps[gi];
-        FigPersist P; fig_persist_of(B, *E.g, P);
-        fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-        const int reach = fig_gap_probe<LDS_TAB>(E);
-        if (E.tid == 0) B.gapctl[gi * 4 + 3] = reach;
-        __syncthreads();
-    }
+    fig_pop_loop(E, B, A, [&] { return fig_src_order(B, A); }, [&](int gi) { fig_item_probe<LDS_TAB>(E, work, gi); });
 }
 
-// ---- kernel 2: speculative candidate evaluations; items = {gap, candidate index j, slot, -}
+// ---- kernel 2: speculative candidate evaluations; items = FigItem records (passed as int4 *, like fig_replay_kernel's: the symbols stay)
+static_assert(sizeof(FigItem) == sizeof(int4) && sizeof(FigEntry) == sizeof(int4), "item records travel as int4");
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_eval_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A, const int4 *items, int n_items) {
     FigEng E; FigScr work;
     fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     FIG_PROF_BEGIN();
-    while (true) {
-        const int qi = fig_queue_pop(E, B, A);
-        if (qi >= n_items) break;
-        int4 it = items[qi];
-        E.g = &B.gaps[it.x];
-        FigPersist P; fig_persist_of(B, *E.g, P);
-        fig_spec_eval<LDS_TAB>(E, work, P, it.y, it.z, E.g->capGg);
-        __syncthreads();
-    }
+    fig_pop_loop(E, B, A, [&] { return FigItemSrc<FigItem>{(const FigItem *)items, 0, n_items}; }, [&](FigItem it) { fig_item_eval<LDS_TAB>(E, work, it); });
     FIG_PROF_FLUSH();
     fig_kernel_flush(E, B);
 }
 
-// ---- kernel 3: replay the bookkeeping of the speculated candidates in order; entries = {gap, n slots, -, -}
+// ---- kernel 3: replay the bookkeeping of the speculated candidates in order, one workgroup per entry
 // One wave, no class: it touches FigState alone, and its launch asks for no more LDS than that.  fig_eng_carve would place gs /
 // rb / plb behind FigState, outside that request, so this kernel keeps them null (a stray use faults instead of corrupting).
 __global__ void __launch_bounds__(64) fig_replay_kernel(FigDevModel M, FigDevBatch B, const int4 *entries, int n) {
     if ((int)blockIdx.x >= n) return;
-    FigEng E; FigScr work;
-    memset(&work, 0, sizeof(work));
-    E.tid = threadIdx.x; E.nt = blockDim.x; E.lane = threadIdx.x & 63; E.wave = 0; E.nw = 1; E.wsz = 64;
-    E.M = &M; E.B = &B; E.capG = 0; E.flops = 0; E.mle_alg = 0; E.mle_exec = 0; E.wait_cycles = 0; E.ncolE = 0; E.xoff = 0; E.Wcap = 0; E.nteams = 1; E.sh_on = 0;
-    E.pq = nullptr; E.q4 = nullptr; E.wbuf = nullptr; E.gs = nullptr; E.rb = nullptr; E.plb = nullptr; E.off_plb = 0; E.pq_lds = 0; E.w_lds = 0;
-    E.off_pq = E.off_q4 = E.off_w = 0; E.tiles = E.tile_step = E.tile_cols = 0; E.lds_tw = 0;
-    E.S = (FigState *)fig_lds;
-    int4 en = entries[blockIdx.x];
-    E.g = &B.gaps[en.x];
-    FigPersist P; fig_persist_of(B, *E.g, P);
-    fig_spec_replay(E, work, P, en.y, E.g->capGg);
-    if (E.tid == 0) { B.gapctl[en.x * 4] = E.S->L.done ? 2 : 1; B.gapctl[en.x * 4 + 1] = E.S->L.j; B.gapctl[en.x * 4 + 2] = E.S->L.range; }
+    FigEng E{}; FigScr work{};
+    fig_eng_ident(E, threadIdx.x, blockDim.x, 64);
+    E.M = &M; E.B = &B; E.nteams = 1; E.S = (FigState *)fig_lds;
+    const FigEntry en = ((const FigEntry *)entries)[blockIdx.x];
+    fig_item_replay(E, work, en);
 }
 
 // ---- kernel 4: fallbacks + finalize + output for the gaps whose loop is done; list = gap ids
@@ -178,18 +139,7 @@ template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_end_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A, const int *list, int n) {
     FigEng E; FigScr work;
     fig_kernel_begin(E, M, B, A, LDS_TAB, work);
-    while (true) {
-        const int qi = fig_queue_pop(E, B, A);
-        if (qi >= n) break;
-        int gi = list[qi];
-        E.g = &B.gaps[gi];
-        FigPersist P; fig_persist_of(B, *E.g, P);
-        fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-        fig_state_load(E, P);
-        fig_gap_end<LDS_TAB>(E);
-        if (E.tid == 0) B.gapctl[gi * 4] = 0;
-        __syncthreads();
-    }
+    fig_pop_loop(E, B, A, [&] { return FigItemSrc<int>{list, 0, n}; }, [&](int gi) { fig_item_end<LDS_TAB>(E, work, gi); });
     fig_kernel_flush(E, B);
 }
 
@@ -229,15 +179,20 @@ __global__ void __launch_bounds__(256) fig_stream_kernel(FigDevModel M, FigDevBa
 // ------------------------------------------------------------------------------------- context
 #define FIG_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { ctx->last_hip = (int)_e; return FIG_EHIP; } } while (0)
 
-struct DevBuf {
-    void *p = nullptr; size_t n = 0;
+struct DevBuf { void *p = nullptr; };
+
+// Device buffers that live for one call: whatever way the call returns, they are freed.
+struct FigTmpBufs {
+    std::vector<void *> bufs;
+    ~FigTmpBufs() { for (void *p : bufs) hipFree(p); }
+    void *alloc(size_t n) { void *p = nullptr; if (hipMalloc(&p, n ? n : 8) != hipSuccess) return nullptr; bufs.push_back(p); return p; }
 };
 
 // Per-class scheduling lane: the classes of a batch run concurrently, each on its own stream with its own work
 // queue head, scratch slabs and item buffers, so that the tail of one class's round is filled by the other
 // classes' workgroups.
-struct FigLane { hipStream_t stream = nullptr; hipEvent_t done = nullptr; int32_t *queue_head = nullptr; uint8_t *scratch = nullptr; int *d_items = nullptr, *d_entries = nullptr; size_t cap = 0;
-                 int32_t *h_ctl = nullptr; int *h_items = nullptr, *h_entries = nullptr; int qsel = 0; };   // h_*: pinned, so the copies run on the DMA engines and never wait for a CU
+struct FigLane { hipStream_t stream = nullptr; hipEvent_t done = nullptr; int32_t *queue_head = nullptr; uint8_t *scratch = nullptr; FigItem *d_items = nullptr; FigEntry *d_entries = nullptr; size_t cap = 0;   // cap: items / entries the buffers hold
+                 FigGapCtl *h_ctl = nullptr; FigItem *h_items = nullptr; FigEntry *h_entries = nullptr; int qsel = 0; };   // h_*: pinned, so the copies run on the DMA engines and never wait for a CU
 
 struct fig_ctx {
     int device = 0;
@@ -252,7 +207,6 @@ struct fig_ctx {
     // resident batch
     bool have_batch = false;
     FigDevBatch db;
-    std::vector<FigDevGap> h_gaps;
     std::vector<int32_t> h_order;
     struct Cls { FigLaunchClass c; int blocks; int capacity; };
     std::vector<Cls> classes;
@@ -272,7 +226,6 @@ static int dev_alloc(fig_ctx *ctx, size_t bytes, void **out) {
     if (bytes == 0) bytes = 8;
     hipError_t e = hipMalloc(&b.p, bytes);
     if (e != hipSuccess) { ctx->last_hip = (int)e; return FIG_ENOMEM; }
-    b.n = bytes;
     ctx->bufs.push_back(b);
     *out = b.p;
     return FIG_OK;
@@ -414,7 +367,7 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     int prc = fig_pack(m, b, sizeof(FigState), K);
     if (prc) return prc;
     int64_t ng = K.n_gaps;
-    ctx->h_gaps = K.gaps; ctx->h_order = K.order; ctx->h_str_off = K.str_off;
+    ctx->h_order = K.order; ctx->h_str_off = K.str_off;
     ctx->str_total = K.str_total; ctx->n_gaps = ng;
     ctx->n_ureads = (int64_t)K.u_pos.size(); ctx->n_preads = (int64_t)K.p_pos.size();
     ctx->classes.clear();
@@ -430,21 +383,15 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
                                              lc.capG, lc.capGl, lc.ncolE, lc.Wcap, lc.nt, lc.nteams, (int)lc.lds_tab, lc.tiles, lc.tile_cols, lc.lds, lc.q_end - lc.q_begin, per_cu, c.blocks, sizeof(FigState));
         ctx->classes.push_back(c);
     }
-    int capG_s = K.capG, capR = K.capR, capP = K.capP, capC = K.capC;
-    int64_t str_total = K.str_total;
-    int64_t stride = fig_scratch_layout(nullptr, capG_s, capR, capP, capC, K.capW, K.capE, nullptr);
+    int64_t stride = fig_scratch_layout(nullptr, K.capG, K.capR, K.capP, K.capC, K.capW, K.capE, nullptr);
     stride = (stride + 255) & ~255LL;
-    std::vector<FigDevGap> &gaps = K.gaps; std::vector<int32_t> &order = K.order;
-    std::vector<uint32_t> &packed = K.packed; std::vector<uint8_t> &qual = K.qual, &flank = K.flank;
-    std::vector<int32_t> &u_pos = K.u_pos, &u_aux = K.u_aux, &u_len = K.u_len, &p_pos = K.p_pos, &p_aux = K.p_aux, &p_clip = K.p_clip, &p_ref = K.p_ref, &p_len = K.p_len;
-    std::vector<int64_t> &u_woff = K.u_woff, &p_woff = K.p_woff, &p_qoff = K.p_qoff;
 
     // ---- upload
     FigDevBatch &db = ctx->db;
     memset(&db, 0, sizeof(db));
     db.n_gaps = ng;
     int rc;
-#define UP(vec, field) do { rc = dev_upload(ctx, vec, &db.field); if (rc) return rc; } while (0)
+#define UP(vec, field) do { rc = dev_upload(ctx, K.vec, &db.field); if (rc) return rc; } while (0)
     UP(gaps, gaps); UP(order, order); UP(packed, packed); UP(qual, qual); UP(flank, flank);
     UP(u_pos, u.pos); UP(u_aux, u.aux); UP(u_len, u.len); UP(u_woff, u.woff);
     UP(p_pos, p.pos); UP(p_aux, p.aux); UP(p_clip, p.clip); UP(p_ref, p.refpos); UP(p_len, p.len); UP(p_woff, p.woff); UP(p_qoff, p.qoff);
@@ -463,14 +410,14 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     }
     if ((rc = dev_alloc(ctx, (size_t)ng * 4, &p))) return rc; db.filled_len = (int32_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)ng * 4, &p))) return rc; db.gaptofill = (int32_t *)p;
-    if ((rc = dev_alloc(ctx, (size_t)str_total, &p))) return rc; db.str = (char *)p;
+    if ((rc = dev_alloc(ctx, (size_t)K.str_total, &p))) return rc; db.str = (char *)p;
     if ((rc = dev_alloc(ctx, 64 * (ctx->classes.size() + 1), &p))) return rc; db.queue_head = (int32_t *)p;
-    if ((rc = dev_alloc(ctx, 512, &p))) return rc; db.counters = (unsigned long long *)p;
+    if ((rc = dev_alloc(ctx, FIG_CNT_N * sizeof(unsigned long long), &p))) return rc; db.counters = (unsigned long long *)p;
     size_t total_blocks = 0;
     for (const fig_ctx::Cls &c : ctx->classes) total_blocks += (size_t)c.capacity;
     if ((rc = dev_alloc(ctx, (size_t)stride * std::max<size_t>(total_blocks, 1), &p))) return rc; db.scratch = (uint8_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)K.persist_total + 256, &p))) return rc; db.persist = (uint8_t *)p;
-    if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1) * 16, &p))) return rc; db.gapctl = (int32_t *)p;
+    if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl), &p))) return rc; db.gapctl = (FigGapCtl *)p;
     if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1), &p))) return rc; ctx->d_ot = (uint8_t *)p; db.ot_preset = ctx->d_ot;
     ctx->h_ot = K.ot_preset;
     FIG_HIP(hipMemcpyAsync(ctx->d_ot, ctx->h_ot.data(), (size_t)std::max<int64_t>(ng, 1), hipMemcpyHostToDevice, ctx->stream));
@@ -483,18 +430,18 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
             if (hipStreamCreate(&l.stream) != hipSuccess || hipEventCreateWithFlags(&l.done, hipEventDisableTiming) != hipSuccess) return FIG_EHIP;
             l.queue_head = db.queue_head + 16 * (ci + 1);
             l.scratch = db.scratch + (size_t)stride * blk; blk += (size_t)c.capacity;
-            l.cap = (size_t)std::max(c.c.q_end - c.c.q_begin, 1) * 4 * (size_t)(K.nslots + 1);
-            if ((rc = dev_alloc(ctx, l.cap * 4, &p))) return rc; l.d_items = (int *)p;
-            if ((rc = dev_alloc(ctx, l.cap * 4, &p))) return rc; l.d_entries = (int *)p;
-            if (hipHostMalloc((void **)&l.h_ctl, (size_t)std::max<int64_t>(ng, 1) * 16, hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
-            if (hipHostMalloc((void **)&l.h_items, l.cap * 4, hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
-            if (hipHostMalloc((void **)&l.h_entries, l.cap * 4, hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
+            l.cap = (size_t)std::max(c.c.q_end - c.c.q_begin, 1) * (size_t)(K.nslots + 1);
+            if ((rc = dev_alloc(ctx, l.cap * sizeof(FigItem), &p))) return rc; l.d_items = (FigItem *)p;
+            if ((rc = dev_alloc(ctx, l.cap * sizeof(FigEntry), &p))) return rc; l.d_entries = (FigEntry *)p;
+            if (hipHostMalloc((void **)&l.h_ctl, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
+            if (hipHostMalloc((void **)&l.h_items, l.cap * sizeof(FigItem), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
+            if (hipHostMalloc((void **)&l.h_entries, l.cap * sizeof(FigEntry), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
         }
     }
     db.scratch_stride = stride;
-    db.capG = capG_s; db.capR = capR; db.capP = capP; db.capC = capC; db.capW = K.capW; db.capE = K.capE;
+    db.capG = K.capG; db.capR = K.capR; db.capP = K.capP; db.capC = K.capC; db.capW = K.capW; db.capE = K.capE;
     db.n_ureads = ctx->n_ureads;
-    FIG_HIP(hipMemsetAsync(db.counters, 0, 512, ctx->stream));
+    FIG_HIP(hipMemsetAsync(db.counters, 0, FIG_CNT_N * sizeof(unsigned long long), ctx->stream));
     FIG_HIP(hipMemsetAsync(db.queue_head, 0, 64 * (ctx->classes.size() + 1), ctx->stream));
     hipEventRecord(ctx->ev1, ctx->stream);
     FIG_HIP(hipStreamSynchronize(ctx->stream));
@@ -517,15 +464,15 @@ extern "C" int fig_batch_probe_reach(fig_ctx *ctx, uint8_t *reach) {
     if (!ctx->hm.partial_flag || ng == 0) return FIG_OK;
     FigDevBatch db = ctx->db;
     fig_batch_clear_planes(db);
-    FIG_HIP(hipMemsetAsync(db.gapctl, 0, (size_t)ng * 16, ctx->stream));
+    FIG_HIP(hipMemsetAsync(db.gapctl, 0, (size_t)ng * sizeof(FigGapCtl), ctx->stream));
     for (const fig_ctx::Cls &c : ctx->classes) {
         FIG_HIP(hipMemsetAsync(db.queue_head, 0, 8, ctx->stream));
         FIG_HIP(launch_any(ctx, c, db, ctx->stream, FIG_K_PROBE, c.blocks, nullptr, 0));
     }
-    std::vector<int32_t> ctl((size_t)ng * 4);
-    FIG_HIP(hipMemcpyAsync(ctl.data(), db.gapctl, (size_t)ng * 16, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<FigGapCtl> ctl((size_t)ng);
+    FIG_HIP(hipMemcpyAsync(ctl.data(), db.gapctl, (size_t)ng * sizeof(FigGapCtl), hipMemcpyDeviceToHost, ctx->stream));
     FIG_HIP(hipStreamSynchronize(ctx->stream));
-    for (int64_t g = 0; g < ng; g++) reach[g] = ctl[(size_t)g * 4 + 3] ? 1 : 0;
+    for (int64_t g = 0; g < ng; g++) reach[g] = ctl[g].reach ? 1 : 0;
     return FIG_OK;
 }
 
@@ -559,40 +506,41 @@ static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln, 
         return er;
     };
     if ((e = launch(FIG_K_BEGIN, c.c.q_end - c.c.q_begin, nullptr)) != hipSuccess) return fail(e);
-    int32_t *ctl = ln.h_ctl;
-    const size_t ctl_n = (size_t)ctx->n_gaps * 4;
+    FigGapCtl *ctl = ln.h_ctl;
+    const size_t ctl_bytes = (size_t)ctx->n_gaps * sizeof(FigGapCtl);
     const std::vector<int> ids(ctx->h_order.begin() + c.c.q_begin, ctx->h_order.begin() + c.c.q_end);   // cost-sorted
     FigRound R;
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = now();
     double t_prev = now(); int round = 0, last_items = 0, last_active = 0, last_chunk = 0, n_active_max = 0;
     while (true) {
-        if ((e = hipMemcpyAsync(ctl, db.gapctl, ctl_n * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
+        if ((e = hipMemcpyAsync(ctl, db.gapctl, ctl_bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);
         fig_plan_round(ids, ctl, capacity, c.c.nsplit, ctx->nslots, knobs.minc, knobs.ipw, n_active_max, R);
         if (knobs.log) { double t = now(); fprintf(stderr, "[figsched] capG=%d round %d: active=%d chunk=%d items=%d blocks=%d  %.1f ms\n", c.c.capG, round, last_active, last_chunk, last_items, capacity, t - t_prev); t_prev = t; }
         round++;
         if (R.n_active == 0) break;
         if (ln.cap < R.items.size() || ln.cap < R.entries.size()) return fail(hipErrorOutOfMemory);
-        const int n_items = (int)(R.items.size() / 4), n_ent = (int)(R.entries.size() / 4);
+        const int n_items = (int)R.items.size(), n_ent = (int)R.entries.size();
+        const size_t items_bytes = R.items.size() * sizeof(FigItem), ent_bytes = R.entries.size() * sizeof(FigEntry);
         last_items = n_items; last_active = R.n_active; last_chunk = R.chunk;
         if (n_items > 0) {
-            memcpy(ln.h_items, R.items.data(), R.items.size() * 4);
-            if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, R.items.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+            memcpy(ln.h_items, R.items.data(), items_bytes);
+            if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, items_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
             if ((e = launch(FIG_K_EVAL, n_items, ln.d_items)) != hipSuccess) return fail(e);
         }
-        memcpy(ln.h_entries, R.entries.data(), R.entries.size() * 4);
-        if ((e = hipMemcpyAsync(ln.d_entries, ln.h_entries, R.entries.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+        memcpy(ln.h_entries, R.entries.data(), ent_bytes);
+        if ((e = hipMemcpyAsync(ln.d_entries, ln.h_entries, ent_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
         hipLaunchKernelGGL(fig_replay_kernel, dim3(n_ent), dim3(64), sizeof(FigState) + 64, stream, ctx->dm, db, (const int4 *)ln.d_entries, n_ent);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e);
         nl++;
     }
     std::vector<int> endlist;
-    for (int g : ids) if (ctl[(size_t)g * 4] == 2) endlist.push_back(g);
+    for (int g : ids) if (ctl[g].status == FIG_GAP_LOOP_DONE) endlist.push_back(g);
     if (!endlist.empty()) {
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);      // h_items is reused: the last round's upload must have left it
-        memcpy(ln.h_items, endlist.data(), endlist.size() * 4);
-        if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, endlist.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+        memcpy(ln.h_items, endlist.data(), endlist.size() * sizeof(int));      // (a gap id per gap of the lane: the item buffers hold nslots + 1 records per gap)
+        if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, endlist.size() * sizeof(int), hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
         if ((e = launch(FIG_K_END, (int)endlist.size(), ln.d_items)) != hipSuccess) return fail(e);
         if (knobs.log) { const double t0 = now(); hipStreamSynchronize(stream); fprintf(stderr, "[figsched] capG=%d end kernel: %d gaps, %.1f ms (lane done at %.1f ms since its first round)\n", c.c.capG, (int)endlist.size(), now() - t0, now() - t_start); }
     }
@@ -608,69 +556,38 @@ extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fi
     hipSetDevice(ctx->device);
     int64_t ng = ctx->n_gaps;
     FigDevBatch &db = ctx->db;
-    // optional debug / draw planes live in per-call device buffers
-    std::vector<void *> tmp;
-    auto talloc = [&](size_t n, void **p) -> int { if (hipMalloc(p, n ? n : 8) != hipSuccess) return FIG_ENOMEM; tmp.push_back(*p); return FIG_OK; };
-    auto tfree = [&]() { for (void *p : tmp) hipFree(p); };
-    fig_batch_clear_planes(db);
-    void *p;
-    if (out->dbg_n_cand && out->dbg_cand_i && out->dbg_cand_lik && out->dbg_max_cand > 0) {
-        db.dbg_max_cand = out->dbg_max_cand;
-        if (talloc((size_t)ng * 4, &p)) { tfree(); return FIG_ENOMEM; } db.dbg_n_cand = (int32_t *)p;
-        if (talloc((size_t)ng * out->dbg_max_cand * 12, &p)) { tfree(); return FIG_ENOMEM; } db.dbg_cand_i = (int32_t *)p;
-        if (talloc((size_t)ng * out->dbg_max_cand * 8, &p)) { tfree(); return FIG_ENOMEM; } db.dbg_cand_lik = (double *)p;
-        hipMemsetAsync(db.dbg_n_cand, 0, (size_t)ng * 4, ctx->stream);
-        if (out->dbg_n_place) { if (talloc((size_t)ng * 4, &p)) { tfree(); return FIG_ENOMEM; } db.dbg_n_place = (int32_t *)p; hipMemsetAsync(db.dbg_n_place, 0, (size_t)ng * 4, ctx->stream); }
-        if (out->dbg_counts && out->dbg_plane_cols > 0) {
-            const size_t n = (size_t)ng * out->dbg_max_cand * out->dbg_plane_cols * 5 * 8;
-            if (talloc(n, &p)) { tfree(); return FIG_ENOMEM; } db.dbg_counts = (double *)p; db.dbg_plane_cols = out->dbg_plane_cols;
-            hipMemsetAsync(db.dbg_counts, 0, n, ctx->stream);
-        }
-        if (out->dbg_read_maxlv && out->dbg_plane_reads > 0) {
-            const size_t n = (size_t)ng * out->dbg_max_cand * out->dbg_plane_reads * 8;
-            if (talloc(n, &p)) { tfree(); return FIG_ENOMEM; } db.dbg_read_maxlv = (double *)p; db.dbg_plane_reads = out->dbg_plane_reads;
-            hipMemsetAsync(db.dbg_read_maxlv, 0, n, ctx->stream);
-        }
+    // the optional planes live in per-call device buffers
+    FigTmpBufs tmp;
+    std::vector<int32_t> hsup(sup ? (size_t)ctx->str_total * 5 : 0);
+    const std::vector<FigPlane> planes = fig_fill_planes(db, ctx->n_ureads + ctx->n_preads, ctx->str_total, out, sup, hsup.data());
+    auto clear = [&](void *p, int v, size_t n) { return n ? hipMemsetAsync(p, v, n, ctx->stream) : hipSuccess; };
+    auto fetch = [&](void *dst, const void *src, size_t n) { return n ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
+    for (const FigPlane &pl : planes) {
+        if (!(*pl.dev = tmp.alloc(pl.bytes))) return FIG_ENOMEM;
+        if (pl.fill >= 0) FIG_HIP(clear(*pl.dev, pl.fill, pl.bytes));
     }
-    int64_t nr = ctx->n_ureads + ctx->n_preads;
-    if (out->draw_pos && out->draw_isz && out->draw_len) {
-        if (talloc((size_t)nr * 4, &p)) { tfree(); return FIG_ENOMEM; } db.draw_pos = (int32_t *)p;
-        if (talloc((size_t)nr * 4, &p)) { tfree(); return FIG_ENOMEM; } db.draw_isz = (int32_t *)p;
-        if (talloc((size_t)ng * 8, &p)) { tfree(); return FIG_ENOMEM; } db.draw_len = (int32_t *)p;
-        hipMemsetAsync(db.draw_isz, 0, (size_t)nr * 4, ctx->stream);
-    }
-    const size_t sup_n = (size_t)ctx->str_total * 5;
-    if (sup) {                        // per-base read support: one slot per string slot, zero unless fig_gap_end writes it
-        if (talloc(sup_n * 4, &p)) { tfree(); return FIG_ENOMEM; } db.sup_counts = (int32_t *)p;
-        if (talloc((size_t)ng * 4, &p)) { tfree(); return FIG_ENOMEM; } db.sup_origin = (int32_t *)p;
-        hipMemsetAsync(db.sup_counts, 0, sup_n * 4, ctx->stream);
-        hipMemsetAsync(db.sup_origin, 0, (size_t)ng * 4, ctx->stream);
-    }
-    hipMemsetAsync(db.counters, 0, 512, ctx->stream);
+    FIG_HIP(clear(db.counters, 0, FIG_CNT_N * sizeof(unsigned long long)));
     // a previous call that failed half-way may have left queue heads / ping-pong selectors inconsistent: start clean
-    hipMemsetAsync(db.queue_head, 0, 64 * (ctx->classes.size() + 1), ctx->stream);
+    FIG_HIP(clear(db.queue_head, 0, 64 * (ctx->classes.size() + 1)));
     for (auto &l : ctx->lanes) l.qsel = 0;
-    hipMemsetAsync(db.filled_len, 0, (size_t)std::max<int64_t>(ng, 1) * 4, ctx->stream);
-    hipMemsetAsync(db.gaptofill, 0, (size_t)std::max<int64_t>(ng, 1) * 4, ctx->stream);
-    hipMemsetAsync(db.str, 'N', (size_t)ctx->str_total, ctx->stream);
-    hipMemsetAsync(db.gapctl, 0, (size_t)std::max<int64_t>(ng, 1) * 16, ctx->stream);
-    hipEventRecord(ctx->ev0, ctx->stream);
+    FIG_HIP(clear(db.filled_len, 0, (size_t)std::max<int64_t>(ng, 1) * 4));
+    FIG_HIP(clear(db.gaptofill, 0, (size_t)std::max<int64_t>(ng, 1) * 4));
+    FIG_HIP(clear(db.str, 'N', (size_t)ctx->str_total));
+    FIG_HIP(clear(db.gapctl, 0, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl)));
+    FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     int nl = 0;
     const FigKnobs knobs = fig_knobs_from_env(ctx->dm.unmapped);      // read here, on the caller's thread: the lane threads only get the values
     if (knobs.seq) {
-        for (size_t ci = 0; ci < ctx->classes.size(); ci++) {
-            const fig_ctx::Cls &c = ctx->classes[ci];
-            hipMemsetAsync(db.queue_head, 0, 4, ctx->stream);
-            hipError_t e = launch_any(ctx, c, db, ctx->stream, FIG_K_FILL, c.blocks, nullptr, 0);
-            if (e != hipSuccess) { ctx->last_hip = (int)e; tfree(); return FIG_EHIP; }
+        for (const fig_ctx::Cls &c : ctx->classes) {
+            FIG_HIP(clear(db.queue_head, 0, 4));
+            FIG_HIP(launch_any(ctx, c, db, ctx->stream, FIG_K_FILL, c.blocks, nullptr, 0));
             nl++;
         }
     } else {
         // one host thread + stream per class; every lane starts after ev0 and the main stream joins them before ev1
         const size_t nc = ctx->classes.size();
         std::vector<int> rcs(nc, 0);
-        ctx->db = db;
-        for (size_t ci = 0; ci < nc; ci++) hipStreamWaitEvent(ctx->lanes[ci].stream, ctx->ev0, 0);
+        for (size_t ci = 0; ci < nc; ci++) FIG_HIP(hipStreamWaitEvent(ctx->lanes[ci].stream, ctx->ev0, 0));
         if (nc <= 1 || knobs.lanes_serial) {
             for (size_t ci = 0; ci < nc; ci++) rcs[ci] = run_class_parallel(ctx, ctx->classes[ci], ctx->lanes[ci], knobs);
         } else {
@@ -679,63 +596,38 @@ extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fi
             for (auto &t : th) t.join();
         }
         for (size_t ci = 0; ci < nc; ci++) {
-            if (rcs[ci] < 0) { hipDeviceSynchronize(); tfree(); return FIG_EHIP; }
+            if (rcs[ci] < 0) { hipDeviceSynchronize(); return FIG_EHIP; }      // (last_hip set by the lane)
             nl += rcs[ci];
-            hipEventRecord(ctx->lanes[ci].done, ctx->lanes[ci].stream);
-            hipStreamWaitEvent(ctx->stream, ctx->lanes[ci].done, 0);
+            FIG_HIP(hipEventRecord(ctx->lanes[ci].done, ctx->lanes[ci].stream));
+            FIG_HIP(hipStreamWaitEvent(ctx->stream, ctx->lanes[ci].done, 0));
         }
     }
-    hipEventRecord(ctx->ev1, ctx->stream);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->last_hip = (int)e; tfree(); return FIG_EHIP; }
-    float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream)); FIG_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0; FIG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->stats.kernel_ms = ms; ctx->stats.n_launches = nl;
     // ---- results back
-    hipEventRecord(ctx->ev0, ctx->stream);
+    FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     std::vector<char> hstr((size_t)ctx->str_total);
-    hipMemcpyAsync(out->filled_len, db.filled_len, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
-    hipMemcpyAsync(out->gaptofill, db.gaptofill, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (ctx->str_total) hipMemcpyAsync(hstr.data(), db.str, (size_t)ctx->str_total, hipMemcpyDeviceToHost, ctx->stream);
-    unsigned long long cnt[64] = {0};
-    hipMemcpyAsync(cnt, db.counters, 512, hipMemcpyDeviceToHost, ctx->stream);
-    if (db.dbg_n_cand) {
-        hipMemcpyAsync(out->dbg_n_cand, db.dbg_n_cand, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
-        hipMemcpyAsync(out->dbg_cand_i, db.dbg_cand_i, (size_t)ng * out->dbg_max_cand * 12, hipMemcpyDeviceToHost, ctx->stream);
-        hipMemcpyAsync(out->dbg_cand_lik, db.dbg_cand_lik, (size_t)ng * out->dbg_max_cand * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (db.dbg_n_place) hipMemcpyAsync(out->dbg_n_place, db.dbg_n_place, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (db.dbg_counts) hipMemcpyAsync(out->dbg_counts, db.dbg_counts, (size_t)ng * out->dbg_max_cand * out->dbg_plane_cols * 5 * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (db.dbg_read_maxlv) hipMemcpyAsync(out->dbg_read_maxlv, db.dbg_read_maxlv, (size_t)ng * out->dbg_max_cand * out->dbg_plane_reads * 8, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (db.draw_pos) {
-        hipMemcpyAsync(out->draw_pos, db.draw_pos, (size_t)nr * 4, hipMemcpyDeviceToHost, ctx->stream);
-        hipMemcpyAsync(out->draw_isz, db.draw_isz, (size_t)nr * 4, hipMemcpyDeviceToHost, ctx->stream);
-        hipMemcpyAsync(out->draw_len, db.draw_len, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    std::vector<int32_t> hsup(sup ? sup_n : 0);
-    if (sup) {
-        if (sup_n) hipMemcpyAsync(hsup.data(), db.sup_counts, sup_n * 4, hipMemcpyDeviceToHost, ctx->stream);
-        hipMemcpyAsync(sup->origin, db.sup_origin, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    hipEventRecord(ctx->ev1, ctx->stream);
-    e = hipStreamSynchronize(ctx->stream);
-    tfree();
-    if (e != hipSuccess) { ctx->last_hip = (int)e; return FIG_EHIP; }
-    hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    unsigned long long cnt[FIG_CNT_N] = {0};
+    FIG_HIP(fetch(out->filled_len, db.filled_len, (size_t)ng * 4)); FIG_HIP(fetch(out->gaptofill, db.gaptofill, (size_t)ng * 4));
+    FIG_HIP(fetch(hstr.data(), db.str, (size_t)ctx->str_total));
+    FIG_HIP(fetch(cnt, db.counters, sizeof(cnt)));
+    for (const FigPlane &pl : planes) FIG_HIP(fetch(pl.host, *pl.dev, pl.bytes));
+    FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream)); FIG_HIP(hipStreamSynchronize(ctx->stream));
+    FIG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->stats.d2h_ms = ms;
 #ifdef FIG_PROF
-    { const char *nm[14] = {"A.wait", "B.wait", "-", "M.finish", "PR.pre", "PR.estep", "PR.mid", "PR.mle", "PR.post", "A.chain", "A.logexp", "A.work", "B.work", "M.chains"};
-      for (int i = 0; i < 14; i++) fprintf(stderr, "[figprof] %-9s %8.1f Gcycles = %5.1f %% of wave-cycles\n", nm[i], cnt[8 + i] / 1e9, cnt[31] ? 100.0 * cnt[8 + i] / cnt[31] : 0.0);
-      { const char *mn[4] = {"M.setup", "M.hint", "M.rounds", "M.surv"};
-        for (int i = 0; i < 4; i++) fprintf(stderr, "[figprof] %-9s %8.1f Gcycles = %5.1f %% of wave-cycles\n", mn[i], cnt[22 + i] / 1e9, cnt[31] ? 100.0 * cnt[22 + i] / cnt[31] : 0.0); }
-      fprintf(stderr, "[figprof] raw slots:"); for (int i = 0; i < 22; i++) fprintf(stderr, " %d:%.1f", i, cnt[8 + i] / 1e9); for (int i = 22; i < 40; i++) fprintf(stderr, " %d:%.1f", i, cnt[32 + i - 22] / 1e9); fprintf(stderr, "\n");
-      fprintf(stderr, "[figprof] barrier wait %.3f of %.3f wave-Gcycles = %.1f %%\n", cnt[30] / 1e9, cnt[31] / 1e9, cnt[31] ? 100.0 * cnt[30] / cnt[31] : 0.0); }
+    { auto prof = [&](int i) { return cnt[i < FIG_PROF_SPLIT ? FIG_CNT_PROF_LO + i : FIG_CNT_PROF_HI + (i - FIG_PROF_SPLIT)]; };
+      const unsigned long long wave = cnt[FIG_CNT_WAVE];
+      const char *nm[14] = {"A.wait", "B.wait", "-", "M.finish", "PR.pre", "PR.estep", "PR.mid", "PR.mle", "PR.post", "A.chain", "A.logexp", "A.work", "B.work", "M.chains"};
+      for (int i = 0; i < 14; i++) fprintf(stderr, "[figprof] %-9s %8.1f Gcycles = %5.1f %% of wave-cycles\n", nm[i], prof(i) / 1e9, wave ? 100.0 * prof(i) / wave : 0.0);
+      const char *mn[4] = {"M.setup", "M.hint", "M.rounds", "M.surv"};
+      for (int i = 0; i < 4; i++) fprintf(stderr, "[figprof] %-9s %8.1f Gcycles = %5.1f %% of wave-cycles\n", mn[i], prof(14 + i) / 1e9, wave ? 100.0 * prof(14 + i) / wave : 0.0);
+      fprintf(stderr, "[figprof] raw slots:"); for (int i = 0; i < FIG_PROF_SLOTS; i++) fprintf(stderr, " %d:%.1f", i, prof(i) / 1e9); fprintf(stderr, "\n");
+      fprintf(stderr, "[figprof] barrier wait %.3f of %.3f wave-Gcycles = %.1f %%\n", cnt[FIG_CNT_WAIT] / 1e9, wave / 1e9, wave ? 100.0 * cnt[FIG_CNT_WAIT] / wave : 0.0); }
 #endif
-    if (knobs.log) fprintf(stderr, "[figsched] useful flops %.4g, speculative evaluations executed %.4g (%.1f %% discarded)\n", (double)cnt[1], (double)cnt[2], cnt[2] ? 100.0 * (1.0 - ((double)cnt[1] / (double)cnt[2])) : 0.0);
-    ctx->stats.place_calls = (int64_t)cnt[0];
-    ctx->stats.alg_flops = (double)cnt[1];
-    ctx->stats.spec_flops = (double)cnt[2];
-    ctx->stats.mle_alg_flops = (double)cnt[3];
-    ctx->stats.mle_exec_flops = (double)cnt[4];
+    if (knobs.log) fprintf(stderr, "[figsched] useful flops %.4g, speculative evaluations executed %.4g (%.1f %% discarded)\n", (double)cnt[FIG_CNT_FLOPS], (double)cnt[FIG_CNT_SPEC], cnt[FIG_CNT_SPEC] ? 100.0 * (1.0 - ((double)cnt[FIG_CNT_FLOPS] / (double)cnt[FIG_CNT_SPEC])) : 0.0);
+    fig_stats_from_counters(cnt, ctx->stats);
     int rc = fig_compact_results(ng, hstr.data(), ctx->h_str_off.data(), out);
     if (!rc && sup) fig_compact_support(ng, hsup.data(), ctx->h_str_off.data(), out, sup->counts);
     return rc;

@@ -1,7 +1,7 @@
 // fig_abi_host.h -- the host logic of the C ABI (include/figbird_hip.h) that does not touch a device: error strings, model
 // checks and tables, the environment knobs, the round planner of the candidate-parallel scheduler, result compaction.
 // Pure C++ (no HIP): compiled into libfighip.so (fig_abi.hip) and into the one-lane emulation the CPU tests run
-// (tests/emu/fig_emu_abi.cpp), so that every decision below is made in one place and the CPU suite checks the shipped code.
+// (tools/emu/fig_emu_abi.cpp), so that every decision below is made in one place and the CPU suite checks the shipped code.
 #ifndef FIG_ABI_HOST_H
 #define FIG_ABI_HOST_H
 #include <algorithm>
@@ -90,12 +90,52 @@ static inline void fig_model_point(FigDevModel &dm, const FigModelOffsets &o, co
 }
 
 // ------------------------------------------------------------------------------------- batch
-// the optional debug / draw planes of a fill: absent unless the call that launches sets them
+// the optional debug / draw / support planes of a fill: absent unless the call that launches sets them
 static inline void fig_batch_clear_planes(FigDevBatch &db) {
     db.dbg_n_cand = nullptr; db.dbg_cand_i = nullptr; db.dbg_cand_lik = nullptr; db.dbg_max_cand = 0; db.dbg_n_place = nullptr;
     db.draw_pos = db.draw_isz = db.draw_len = nullptr;
     db.dbg_counts = db.dbg_read_maxlv = nullptr; db.dbg_plane_cols = db.dbg_plane_reads = 0;
     db.sup_counts = db.sup_origin = nullptr;
+}
+
+// An optional plane of a fill (fig_gap_results' dbg_* / draw_*, fig_gap_support): the FigDevBatch field the engine writes through, where
+// the caller wants it, its size, and the byte it is cleared to before the launches (< 0: not cleared, the engine writes all that is read).
+struct FigPlane { void **dev; void *host; size_t bytes; int fill; };
+
+// The planes this call asked for, each described once; everything else of db's optional part is switched off.  n_reads:
+// unmapped + partial reads of the batch; sup_host: str_total * 5 int32 (one slot per string slot, compacted afterwards).
+static std::vector<FigPlane> fig_fill_planes(FigDevBatch &db, int64_t n_reads, int64_t str_total, const fig_gap_results *out, const fig_gap_support *sup, int32_t *sup_host) {
+    std::vector<FigPlane> pl;
+    auto add = [&](auto *&dev, void *host, size_t bytes, int fill) { pl.push_back(FigPlane{(void **)&dev, host, bytes, fill}); };
+    const size_t ng = (size_t)db.n_gaps, nr = (size_t)n_reads;
+    fig_batch_clear_planes(db);
+    if (out->dbg_n_cand && out->dbg_cand_i && out->dbg_cand_lik && out->dbg_max_cand > 0) {      // candidate trace
+        const size_t nc = ng * out->dbg_max_cand;
+        db.dbg_max_cand = out->dbg_max_cand;
+        add(db.dbg_n_cand, out->dbg_n_cand, ng * 4, 0);
+        add(db.dbg_cand_i, out->dbg_cand_i, nc * 12, -1);
+        add(db.dbg_cand_lik, out->dbg_cand_lik, nc * 8, -1);
+        if (out->dbg_n_place) add(db.dbg_n_place, out->dbg_n_place, ng * 4, 0);
+        if (out->dbg_counts && out->dbg_plane_cols > 0) { db.dbg_plane_cols = out->dbg_plane_cols; add(db.dbg_counts, out->dbg_counts, nc * out->dbg_plane_cols * 5 * 8, 0); }
+        if (out->dbg_read_maxlv && out->dbg_plane_reads > 0) { db.dbg_plane_reads = out->dbg_plane_reads; add(db.dbg_read_maxlv, out->dbg_read_maxlv, nc * out->dbg_plane_reads * 8, 0); }
+    }
+    if (out->draw_pos && out->draw_isz && out->draw_len) {
+        add(db.draw_pos, out->draw_pos, nr * 4, -1);
+        add(db.draw_isz, out->draw_isz, nr * 4, 0);
+        add(db.draw_len, out->draw_len, ng * 8, -1);
+    }
+    if (sup) {                        // per-base read support: zero unless fig_gap_end writes it
+        add(db.sup_counts, sup_host, (size_t)str_total * 5 * 4, 0);
+        add(db.sup_origin, sup->origin, ng * 4, 0);
+    }
+    return pl;
+}
+
+// fig_stats' counter fields, from a read-back of FigDevBatch::counters
+static inline void fig_stats_from_counters(const unsigned long long *cnt, fig_stats &st) {
+    st.place_calls = (int64_t)cnt[FIG_CNT_PLACE];
+    st.alg_flops = (double)cnt[FIG_CNT_FLOPS]; st.spec_flops = (double)cnt[FIG_CNT_SPEC];
+    st.mle_alg_flops = (double)cnt[FIG_CNT_MLE_ALG]; st.mle_exec_flops = (double)cnt[FIG_CNT_MLE_EXEC];
 }
 
 // the launch arguments of a class (FigKernArgs, fig_engine.h)
@@ -184,25 +224,23 @@ static FigKnobs fig_knobs_from_env(int unmapped) {
 
 // ------------------------------------------------------------------------------------- round planner
 // One round of the candidate-parallel scheduler (fig_engine_sched.h) for one class lane: which active gaps take part and
-// how many candidates each of them evaluates.  entries = {gap, n slots, 0, 0} per admitted gap (one replay each), items =
-// {gap, candidate index j, slot, 0} per evaluation.
-struct FigRound { std::vector<int> items, entries; int chunk = 0, n_active = 0; };
+// how many candidates each of them evaluates.  One entry per admitted gap (one replay each), one item per evaluation.
+struct FigRound { std::vector<FigItem> items; std::vector<FigEntry> entries; int chunk = 0, n_active = 0; };
 
-// ids: the lane's gaps in cost order; ctl: gapctl snapshot ({status, next j, range, -} per gap of the batch); capacity:
-// workgroups the device holds for this class; nsplit: lanes the class runs as; slots_cap: candidate slots per gap;
-// n_active_max: the lane's largest active set so far (in/out).  n_active == 0 on return: nothing left, no round.
-static void fig_plan_round(const std::vector<int> &ids, const int32_t *ctl, int capacity, int nsplit, int slots_cap, int minc, double ipw_base,
+// ids: the lane's gaps in cost order; ctl: gapctl snapshot of the batch; capacity: workgroups the device holds for this class;
+// nsplit: lanes the class runs as; slots_cap: candidate slots per gap; n_active_max: the lane's largest active set so far
+// (in/out).  n_active == 0 on return: nothing left, no round.
+static void fig_plan_round(const std::vector<int> &ids, const FigGapCtl *ctl, int capacity, int nsplit, int slots_cap, int minc, double ipw_base,
                            int &n_active_max, FigRound &R) {
-    std::vector<int> &items = R.items, &entries = R.entries;
-    items.clear(); entries.clear();
+    R.items.clear(); R.entries.clear();
     R.chunk = 0; R.n_active = 0;
-    for (int g : ids) if (ctl[(size_t)g * 4] == 1) R.n_active++;
+    for (int g : ids) if (ctl[g].status == FIG_GAP_MORE) R.n_active++;
     if (R.n_active == 0) return;
     // Candidates per gap this round: proportional to the candidates the gap still has, so that all gaps of the class
     // finish in about the same round and every round carries ~12 items per resident workgroup (of both lanes of a split class).  A gap that stops
     // early discards at most chunk-1 evaluations.
     long long rem_total = 0;
-    for (int g : ids) if (ctl[(size_t)g * 4] == 1) rem_total += std::max(0, ctl[(size_t)g * 4 + 2] - ctl[(size_t)g * 4 + 1]);
+    for (int g : ids) if (ctl[g].status == FIG_GAP_MORE) rem_total += std::max(0, ctl[g].range - ctl[g].j);
     // Round size: `ipw_base` items per resident workgroup while the lane has about a hundred active gaps (the 512-gap bench
     // batch: 12 is its optimum), growing with the lane's number of active gaps (its maximum so far) up to 8x.  Measured on one box (round 3,
     // profiles/round3/largefill_*): the 2048-gap fill of the bench recipe takes 111.9 s with 12 items per workgroup and
@@ -219,19 +257,19 @@ static void fig_plan_round(const std::vector<int> &ids, const int32_t *ctl, int 
     const double target = ipw * capacity / (double)std::max(1, nsplit);
     long long total = 0;
     for (int g : ids) {
-        if (ctl[(size_t)g * 4] != 1) continue;
+        if (ctl[g].status != FIG_GAP_MORE) continue;
         if ((double)total >= 1.25 * target) break;           // the rest waits for a later round
-        int j = ctl[(size_t)g * 4 + 1], range = ctl[(size_t)g * 4 + 2];
+        int j = ctl[g].j, range = ctl[g].range;
         int want = (int)std::ceil((range - j) * share);
         want = std::min(std::max(want, minc), slots_cap);
         int n = std::max(0, std::min(want, range - j));       // (0: replayed with nothing to evaluate: the replay closes the gap)
         R.chunk = std::max(R.chunk, n);
         total += n;
-        entries.push_back(g); entries.push_back(n); entries.push_back(0); entries.push_back(0);
+        R.entries.push_back(FigEntry{g, n, 0, 0});
     }
     // items gap-major in descending-cost gap order (longest processing time first keeps the round's tail short)
-    for (size_t q = 0; q < entries.size(); q += 4)
-        for (int k = entries[q + 1] - 1; k >= 0; k--) { int g = entries[q]; items.push_back(g); items.push_back(ctl[(size_t)g * 4 + 1] + k); items.push_back(k); items.push_back(0); }
+    for (const FigEntry &en : R.entries)
+        for (int k = en.n - 1; k >= 0; k--) R.items.push_back(FigItem{en.gap, ctl[en.gap].j + k, k, 0});
 }
 
 #endif

@@ -74,7 +74,7 @@ FIG_D unsigned long long fig_shfl_down_u64(unsigned long long v, int off) { retu
 #define FIG_PLB_BYTES (FIG_PLB_TEAMS * 64 * 4)
 
 // Optional phase timers (diagnostic build only: -DFIG_PROF).  Every lane accumulates s_memtime deltas in its own
-// FigEng::prof[] (no atomics inside the loops); lane 0 of each wave adds them to B.counters[8+slot] when the kernel
+// FigEng::prof[] (no atomics inside the loops); lane 0 of each wave adds them to its FIG_CNT_PROF_* counter when the kernel
 // ends, so the printed figures are sums over WAVES.  Never enabled in the shipped library.
 #if defined(FIG_PROF) && !defined(FIG_EMU)
 #define FIG_T0(E) unsigned long long _fig_t = __builtin_readcyclecounter()
@@ -294,8 +294,14 @@ struct FigEng {
     unsigned long long mle_alg;      // per-lane share of `flops` credited to the MLE passes (1 per placement and base)
     unsigned long long mle_exec;     // FP64 multiplies the MLE passes actually executed after pruning (wave total, kept in lane 0)
     unsigned long long wait_cycles;  // FIG_PROF only: cycles spent in workgroup barriers
-    unsigned long long prof[40];     // FIG_PROF only: phase timers
+    unsigned long long prof[FIG_PROF_SLOTS];   // FIG_PROF only: phase timers
 };
+
+// Who a lane is: thread `tid` of `nt`, in waves of `wsz` lanes (64 on the device, 1 in the one-lane emulation).
+FIG_D void fig_eng_ident(FigEng &E, unsigned tid, unsigned nt, unsigned wsz) {
+    E.tid = (int)tid; E.nt = (int)nt;
+    E.lane = (int)(tid % wsz); E.wave = (int)(tid / wsz); E.nw = (int)((nt + wsz - 1) / wsz); E.wsz = (int)wsz;
+}
 
 // What a launch hands its workgroups besides model and batch: the class's capacities and memory form, the queue range.
 struct FigKernArgs { int capG, capGl, ncolE, Wcap, nteams, q_begin, q_end, qsel, tiles, tile_step, tile_cols, tiled_max, sh_on; };

@@ -297,9 +297,9 @@ FIG_D void fig_gap_end(FigEng &E) {
     }
     if (E.tid == 0) {
         E.B->filled_len[g.gapNo] = len; E.B->gaptofill[g.gapNo] = S.gaptofill;
-        fig_atomic_add_u64(&E.B->counters[0], (unsigned long long)S.n_place);
+        fig_atomic_add_u64(&E.B->counters[FIG_CNT_PLACE], (unsigned long long)S.n_place);
         if (E.B->dbg_n_place) E.B->dbg_n_place[g.gapNo] = S.n_place;
-        if (S.flops_useful) fig_atomic_add_u64(&E.B->counters[1], S.flops_useful);
+        if (S.flops_useful) fig_atomic_add_u64(&E.B->counters[FIG_CNT_FLOPS], S.flops_useful);
     }
     FIG_SYNC();
 }
@@ -441,7 +441,7 @@ FIG_D void fig_spec_eval(FigEng &E, const FigScr &work, const FigPersist &P, int
         for (int off = 32; off > 0; off >>= 1) d += fig_shfl_down_u64(d, off);
         if (E.lane != 0) d = 0;
 #endif
-        if (d) { fig_atomic_add_u64(&fig_slot_hdr(P, slot)->flops, d); fig_atomic_add_u64(&E.B->counters[2], d); }
+        if (d) { fig_atomic_add_u64(&fig_slot_hdr(P, slot)->flops, d); fig_atomic_add_u64(&E.B->counters[FIG_CNT_SPEC], d); }
     }
     E.flops = flops0;                             // speculative work is credited by the replay, and only if it is consumed
     FIG_SYNC();
@@ -480,5 +480,87 @@ FIG_D void fig_spec_replay(FigEng &E, const FigScr &work, const FigPersist &P, i
         fig_loop_step(E);
     }
     fig_state_save(E, P);
+}
+
+// =======================================================================================
+// The work-item protocol: what a workgroup does with one popped item, and what it publishes for the round planner
+// (fig_abi_host.h).  The persistent kernels (fig_abi.hip) and the one-lane emulation (tests/emu) both run exactly these.
+// Every function takes the workgroup's own carve-up of its scratch slab (`work`) and does everything between two pops.
+FIG_D void fig_persist_of(const FigDevBatch &B, const FigDevGap &g, FigPersist &P) {
+    fig_persist_layout(B.persist + g.persistOff, g.capGg, g.nU, g.nP, g.rangeCap, g.nslots, sizeof(FigState), &P);
+}
+
+// E.g, the gap's persistent slab and the whole-gap binding of the scratch arrays
+FIG_D void fig_item_gap(FigEng &E, const FigScr &work, int gi, FigPersist &P) {
+    E.g = &E.B->gaps[gi];
+    fig_persist_of(*E.B, *E.g, P);
+    fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
+}
+
+// the gap's control word; publish: where its candidate loop stands, for the planner
+FIG_D FigGapCtl &fig_ctl_of(const FigEng &E, int gi) { return *(E.B->gapctl + gi); }
+FIG_D void fig_ctl_publish(const FigEng &E, int gi) {
+    if (E.tid != 0) return;
+    FigGapCtl &c = fig_ctl_of(E, gi);
+    c.status = E.S->L.done ? FIG_GAP_LOOP_DONE : FIG_GAP_MORE; c.j = E.S->L.j; c.range = E.S->L.range;
+}
+
+// sequential mode: the whole gap
+template <bool LDS>
+FIG_D void fig_item_fill(FigEng &E, const FigScr &work, int gi) {
+    FigPersist P; fig_item_gap(E, work, gi, P);
+    fig_fill_gap<LDS>(E);
+}
+
+// setup + analyzeGap + checkGapReads; a gap that is not filled (:6227) makes its one pass without EM and finishes here
+template <bool LDS>
+FIG_D void fig_item_begin(FigEng &E, const FigScr &work, int gi) {
+    FigPersist P; fig_item_gap(E, work, gi, P);
+    fig_gap_begin<LDS>(E);
+    if (!E.S->L.inr) {
+        while (!E.S->L.done) { fig_eval_candidate<LDS>(E); fig_loop_step(E); }
+        fig_gap_end<LDS>(E);
+        if (E.tid == 0) fig_ctl_of(E, gi).status = FIG_GAP_FINISHED;
+    } else {
+        fig_state_save(E, P);
+        fig_ctl_publish(E, gi);
+    }
+    FIG_SYNC();
+}
+
+// pre-pass (partial mode): does the gap's candidate loop get to Figbird.cpp:6317?
+template <bool LDS>
+FIG_D void fig_item_probe(FigEng &E, const FigScr &work, int gi) {
+    FigPersist P; fig_item_gap(E, work, gi, P);
+    const int reach = fig_gap_probe<LDS>(E);
+    if (E.tid == 0) fig_ctl_of(E, gi).reach = reach;
+    FIG_SYNC();
+}
+
+// one speculative candidate evaluation
+template <bool LDS>
+FIG_D void fig_item_eval(FigEng &E, const FigScr &work, const FigItem &it) {
+    E.g = &E.B->gaps[it.gap];
+    FigPersist P; fig_persist_of(*E.B, *E.g, P);
+    fig_spec_eval<LDS>(E, work, P, it.j, it.slot, E.g->capGg);
+    FIG_SYNC();
+}
+
+// the bookkeeping of the gap's speculated candidates, in order
+FIG_D void fig_item_replay(FigEng &E, const FigScr &work, const FigEntry &en) {
+    E.g = &E.B->gaps[en.gap];
+    FigPersist P; fig_persist_of(*E.B, *E.g, P);
+    fig_spec_replay(E, work, P, en.n, E.g->capGg);
+    fig_ctl_publish(E, en.gap);
+}
+
+// fallbacks + finalize + output of a gap whose loop is done
+template <bool LDS>
+FIG_D void fig_item_end(FigEng &E, const FigScr &work, int gi) {
+    FigPersist P; fig_item_gap(E, work, gi, P);
+    fig_state_load(E, P);
+    fig_gap_end<LDS>(E);
+    if (E.tid == 0) fig_ctl_of(E, gi).status = FIG_GAP_FINISHED;
+    FIG_SYNC();
 }
 #endif

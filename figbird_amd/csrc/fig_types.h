@@ -1,4 +1,4 @@
-// fig_types.h -- POD descriptors shared by the host packer (fig_abi.cpp) and the gfx950
+// fig_types.h -- POD descriptors shared by the host packer (fig_pack.h, fig_abi.hip) and the gfx950
 // gap-fill engine (fig_engine.h).  Everything here is plain data laid out for HBM:
 //  * read bases are packed 2 bits/base (A0 C1 G2 T3) in 32-bit words, 16 bases per word,
 //    followed by a 1 bit/base N-mask (32 bases per word); a read's words are contiguous so a
@@ -24,6 +24,27 @@
 
 // Path mask of a gap's support plane (FigDevBatch::sup_origin); the values of the public FIG_SUP_* (fig_abi_host.h asserts it)
 enum { FIG_ORG_NONE = 0, FIG_ORG_FINAL = 1, FIG_ORG_ORIGINAL = 2, FIG_ORG_TIEBREAK = 4 };
+
+// Control word of one gap in the candidate-parallel scheduler: the begin and replay items publish it (fig_ctl_publish,
+// fig_engine_sched.h), the round planner (fig_abi_host.h) reads a snapshot of all of them.
+enum { FIG_GAP_FINISHED = 0, FIG_GAP_MORE = 1, FIG_GAP_LOOP_DONE = 2 };   // output written ; candidates left to evaluate ; loop over, the end item is due
+struct FigGapCtl { int32_t status, j, range, reach; };                    // FIG_GAP_*, next candidate index, candidate count, reach bit of the probe item
+
+// Work items of a round, as the planner lays them out and the kernels read them (one 16-byte load each)
+struct alignas(16) FigItem { int32_t gap, j, slot, pad; };                 // evaluate candidate j of the gap into slot
+struct alignas(16) FigEntry { int32_t gap, n, pad0, pad1; };               // replay the gap's slots 0..n-1
+static_assert(sizeof(FigGapCtl) == 16 && sizeof(FigItem) == 16 && sizeof(FigEntry) == 16, "control words are four int32: buffers and copies are sized by sizeof");
+
+enum FigCounter {                    // slots of FigDevBatch::counters
+    FIG_CNT_PLACE = 0,               // placeReads calls of the candidates the gaps' loops consumed
+    FIG_CNT_FLOPS = 1, FIG_CNT_SPEC = 2,         // algorithmic flops: useful work only ; every speculative evaluation executed, discarded ones included
+    FIG_CNT_MLE_ALG = 3, FIG_CNT_MLE_EXEC = 4,   // MLE passes: flops credited ; FP64 multiplies executed after pruning (raw totals, only their ratio is reported)
+    // FIG_PROF build: FigEng::prof[i] is counter PROF_LO + i below FIG_PROF_SPLIT, PROF_HI + (i - FIG_PROF_SPLIT) from it on; cycles in barriers; wave-cycles
+    FIG_CNT_PROF_LO = 8, FIG_CNT_WAIT = 30, FIG_CNT_WAVE = 31, FIG_CNT_PROF_HI = 32,
+    FIG_CNT_N = 64
+};
+#define FIG_PROF_SLOTS 40
+#define FIG_PROF_SPLIT 22
 
 struct FigDevModel {
     int32_t L;                       // maxReadLength
@@ -79,14 +100,14 @@ struct FigDevBatch {
     int32_t *draw_pos, *draw_isz, *draw_len; int64_t n_ureads;
     int32_t dbg_plane_cols, dbg_plane_reads; double *dbg_counts, *dbg_read_maxlv;   // numeric planes (i)/(ii), parity tests only
     // work queue + counters
-    int32_t *queue_head;             // [1] next index into order[]
-    unsigned long long *counters;    // [0] placeReads calls, [1] algorithmic flops (as integer count)
+    int32_t *queue_head;             // [2] a persistent launch pops from [FigKernArgs::qsel] and zeroes the other for its successor
+    unsigned long long *counters;    // [FIG_CNT_N], by FigCounter
     // scratch
     uint8_t *scratch; int64_t scratch_stride;   // one slab per workgroup
     int32_t capG, capR, capP, capC;  // capacities the slab was carved for (columns, unmapped reads, partial reads, candidates)
     int32_t capW, capE;              // weight-buffer doubles, extended-table columns
     uint8_t *persist;                // per-gap persistent slabs
-    int32_t *gapctl;                 // [n_gaps*4] {status (0 finished, 1 more candidates, 2 loop done), next j, range, reach bit of fig_probe_kernel}
+    FigGapCtl *gapctl;               // [n_gaps]
     const uint8_t *ot_preset;        // [n_gaps] 1 = the gap's worker process has set overlap_threshold before it gets to the gap (Figbird.cpp:103, :6317)
     // optional per-base read support (fig_gap_support): the countsGap columns behind the emitted string, [(strOff + x) * 5 + b],
     // and the FIG_ORG_* path mask per gap; both null = off (fig_gap_end takes one uniform branch and stores nothing)

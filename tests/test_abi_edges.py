@@ -1,6 +1,7 @@
 """C-ABI edge behaviour: empty batches, invalid descriptors, inputs outside the supported envelope.
 Runs against the emulation library on CPU and against libfighip.so on the GPU (same ctypes structs)."""
 import copy
+import ctypes as C
 import os
 
 import numpy as np
@@ -86,6 +87,25 @@ def _edge_checks(lib_path, tmp_path):
         with pytest.raises(RuntimeError, match="invalid argument"):
             eng.set_model_struct(cm)
     eng.set_model(model)
+    # a result string buffer one byte short of what the fill needs -> FIG_ENOSPC, returned after the launches: the one
+    # error of the suite that leaves fig_fill_resident past its per-call device buffers (the draw planes here)
+    eng.upload(batch)
+    ok = eng.fill_resident()
+    n, need = batch.n_gaps, int(ok.str_off[batch.n_gaps])
+    assert need == sum(len(s) for s in ok.strings) and need > 0
+    nr = int(batch.u_read_off[-1]) + int(batch.p_read_off[-1])
+    fl = np.zeros(n, dtype=np.int32); gt = np.zeros(n, dtype=np.int32); so = np.zeros(n + 1, dtype=np.int64); st = np.zeros(need, dtype=np.uint8)
+    dpos = np.zeros(max(nr, 1), dtype=np.int32); disz = np.zeros(max(nr, 1), dtype=np.int32); dlen = np.zeros(2 * n, dtype=np.int32)
+    r = api.FigGapResults()
+    r.filled_len = api._p(fl, api.c_i32_p); r.gaptofill = api._p(gt, api.c_i32_p); r.str_off = api._p(so, api.c_i64_p)
+    r.str = C.cast(st.ctypes.data, C.c_char_p); r.str_capacity = need - 1
+    r.draw_pos = api._p(dpos, api.c_i32_p); r.draw_isz = api._p(disz, api.c_i32_p); r.draw_len = api._p(dlen, api.c_i32_p)
+    rc = eng.lib.fig_fill_resident(eng.ctx, C.byref(r))
+    assert rc != 0 and eng.lib.fig_strerror(rc).decode() == "result string buffer too small"
+    assert list(fl) == list(ok.filled_len)                       # the fill itself ran; only the strings did not fit
+    r.str_capacity = need                                         # and exactly enough is enough
+    assert eng.lib.fig_fill_resident(eng.ctx, C.byref(r)) == 0 and st.tobytes().decode() == "".join(ok.strings)
+    eng.free_batch()
     # the engine is still usable after the errors and gives the same answer as before them
     r1 = eng.fill(batch)
     r2 = eng.fill(batch)

@@ -1,7 +1,8 @@
 """Build the TEST INFRASTRUCTURE (never shipped, never imported by the product package figbird_amd/):
 the oracle restatement (oracle/figbird_oracle), the reference binaries compiled from the sources where they lie
 (oracle/_ref/, only where /root/reference exists -- the GPU box uses the prebuilt files), and the one-lane host
-emulation of the device engine used by the CPU unit tests (tests/emu/)."""
+emulation of the device engine used by the CPU unit tests (source: tools/emu/, next to this builder, because it follows the
+engine's internal interfaces; binaries: tests/emu/)."""
 from __future__ import annotations
 
 import os
@@ -29,7 +30,8 @@ def build(force: bool = False) -> None:
     hsrcs = sorted(os.path.join(host, f) for f in os.listdir(host) if f.endswith((".cpp", ".h")))
     main_cpp = os.path.join(host, "figfill_main.cpp")
     host_cpps = [f for f in hsrcs if f.endswith(".cpp") and os.path.basename(f).startswith("fig_")]
-    emu_abi = os.path.join(ROOT, "tests", "emu", "fig_emu_abi.cpp")
+    emu_abi = os.path.join(ROOT, "tools", "emu", "fig_emu_abi.cpp")
+    os.makedirs(os.path.dirname(EMU), exist_ok=True)
     srcs = hsrcs + [emu_abi] + fbuild._csrc_files()
     if force or not fbuild._newer(EMU, srcs):
         fbuild._run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "-o", EMU, main_cpp] + host_cpps + [emu_abi])

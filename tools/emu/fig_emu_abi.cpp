@@ -90,16 +90,13 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
     std::vector<int32_t> fl(ng + 1, 0), gtf(ng + 1, 0);
     std::vector<char> str((size_t)K.str_total + 8, 'N');
     B.filled_len = fl.data(); B.gaptofill = gtf.data(); B.str = str.data();
-    if (out->dbg_n_cand && out->dbg_cand_i && out->dbg_cand_lik && out->dbg_max_cand > 0) {
-        B.dbg_max_cand = out->dbg_max_cand; B.dbg_n_cand = out->dbg_n_cand; B.dbg_cand_i = out->dbg_cand_i; B.dbg_cand_lik = out->dbg_cand_lik;
-        for (int64_t g = 0; g < ng; g++) out->dbg_n_cand[g] = 0;
-        B.dbg_n_place = out->dbg_n_place;
-        if (out->dbg_counts && out->dbg_plane_cols > 0) { B.dbg_counts = out->dbg_counts; B.dbg_plane_cols = out->dbg_plane_cols; memset(out->dbg_counts, 0, (size_t)ng * out->dbg_max_cand * out->dbg_plane_cols * 5 * 8); }
-        if (out->dbg_read_maxlv && out->dbg_plane_reads > 0) { B.dbg_read_maxlv = out->dbg_read_maxlv; B.dbg_plane_reads = out->dbg_plane_reads; memset(out->dbg_read_maxlv, 0, (size_t)ng * out->dbg_max_cand * out->dbg_plane_reads * 8); }
+    // the optional planes are written in place: the engine's pointers are the caller's buffers
+    for (const FigPlane &pl : fig_fill_planes(B, (int64_t)(K.u_pos.size() + K.p_pos.size()), K.str_total, out, nullptr, nullptr)) {
+        *pl.dev = pl.host;
+        if (pl.fill >= 0) memset(pl.host, pl.fill, pl.bytes);
     }
-    if (out->draw_pos && out->draw_isz && out->draw_len) { B.draw_pos = out->draw_pos; B.draw_isz = out->draw_isz; B.draw_len = out->draw_len; }
     B.n_ureads = (int64_t)K.u_pos.size();
-    int32_t qh = 0; unsigned long long counters[8] = {0};
+    int32_t qh = 0; unsigned long long counters[FIG_CNT_N] = {0};
     B.queue_head = &qh; B.counters = counters;
     long long stride = fig_scratch_layout(nullptr, K.capG, K.capR, K.capP, K.capC, K.capW, K.capE, nullptr);
     std::vector<unsigned char> slab((size_t)stride + 64, 0);
@@ -107,8 +104,8 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
     B.capG = K.capG; B.capR = K.capR; B.capP = K.capP; B.capC = K.capC; B.capW = K.capW; B.capE = K.capE;
     std::vector<unsigned char> persist((size_t)K.persist_total + 256, 0);
     B.persist = persist.data();
-    std::vector<int32_t> gapctl((size_t)ng * 4 + 4, 0);
-    B.gapctl = gapctl.data();
+    std::vector<FigGapCtl> ctl((size_t)ng + 1, FigGapCtl{0, 0, 0, 0});
+    B.gapctl = ctl.data();
     B.ot_preset = K.ot_preset.data();
     const FigDevModel &M = ctx->dm;
     const FigKnobs knobs = fig_knobs_from_env(M.unmapped);
@@ -124,7 +121,7 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
             fprintf(stderr, "[figemu] class ncolE=%d: LDS-tiled E-step forced, tiles=%d step=%d cols=%d\n", c.ncolE, A.tiles, A.tile_step, A.tile_cols);
         }
         FigEng E;
-        E.tid = 0; E.nt = 1; E.lane = 0; E.wave = 0; E.nw = 1; E.wsz = 1;
+        fig_eng_ident(E, 0, 1, 1);
         E.M = &ctx->dm; E.B = &B; E.flops = 0; E.mle_alg = 0; E.mle_exec = 0;
         fig_scratch_layout(slab.data(), K.capG, K.capR, K.capP, K.capC, K.capW, K.capE, &E.scr);
         // the "LDS" of the workgroup: the layout is asked for its size first, then laid out again on the buffer of that size
@@ -132,36 +129,17 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
         std::vector<double> lds((size_t)(fig_eng_carve(E, M, A, true) + 7) / 8, 0.0);
         fig_lds = lds.data();
         fig_eng_carve(E, M, A, true);
-        FigScr work = E.scr;
-        auto persist_of = [&](const FigDevGap &g, FigPersist &P) { fig_persist_layout(B.persist + g.persistOff, g.capGg, g.nU, g.nP, g.rangeCap, g.nslots, sizeof(FigState), &P); };
+        const FigScr work = E.scr;
         auto poison = [&] { memset(slab.data(), 0xA5, slab.size()); memset(lds.data(), 0xA5, lds.size() * sizeof(double)); };
-        auto publish = [&](int gi) { gapctl[(size_t)gi * 4] = E.S->L.done ? 2 : 1; gapctl[(size_t)gi * 4 + 1] = E.S->L.j; gapctl[(size_t)gi * 4 + 2] = E.S->L.range; };
+        // the work items of fig_engine_sched.h, in the order the kernels of fig_abi.hip would pop them
+        const std::vector<int> ids(K.order.begin() + c.q_begin, K.order.begin() + c.q_end);
         if (probe_reach) {
-            for (int qi = c.q_begin; qi < c.q_end; qi++) {
-                E.g = &K.gaps[K.order[qi]];
-                FigPersist P; persist_of(*E.g, P);
-                fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-                probe_reach[K.order[qi]] = fig_gap_probe<true>(E) ? 1 : 0;
-            }
+            for (int gi : ids) { fig_item_probe<true>(E, work, gi); probe_reach[gi] = ctl[gi].reach ? 1 : 0; }
         } else if (knobs.seq) {
-            for (int qi = c.q_begin; qi < c.q_end; qi++) {
-                E.g = &K.gaps[K.order[qi]];
-                FigPersist P; persist_of(*E.g, P);
-                fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-                fig_fill_gap<true>(E);
-            }
+            for (int gi : ids) fig_item_fill<true>(E, work, gi);
         } else {
-            // candidate-parallel schedule: the rounds fig_plan_round lays out, executed in order (the roles of the begin, eval,
-            // replay and end kernels)
-            const std::vector<int> ids(K.order.begin() + c.q_begin, K.order.begin() + c.q_end);
-            for (int gi : ids) {
-                E.g = &K.gaps[gi];
-                FigPersist P; persist_of(*E.g, P);
-                fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-                fig_gap_begin<true>(E);
-                if (!E.S->L.inr) { while (!E.S->L.done) { fig_eval_candidate<true>(E); fig_loop_step(E); } fig_gap_end<true>(E); gapctl[(size_t)gi * 4] = 0; }
-                else { fig_state_save(E, P); publish(gi); }
-            }
+            // candidate-parallel schedule: the rounds fig_plan_round lays out, executed in order
+            for (int gi : ids) fig_item_begin<true>(E, work, gi);
             // Knobs as in the library, with a stand-in of 8 resident workgroups for the device's capacity: small enough that
             // the admission cut-off leaves gaps waiting in batches of a few dozen gaps.  Results do not depend on it, nor on
             // the chunk -- that is the invariant under test.  FIG_EMU_CHUNK=<n>: exactly min(n, nslots, range - j)
@@ -171,37 +149,18 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
             FigRound R;
             int n_active_max = 0;
             while (true) {
-                fig_plan_round(ids, gapctl.data(), 8, c.nsplit, slots_cap, minc, knobs.ipw, n_active_max, R);
+                fig_plan_round(ids, ctl.data(), 8, c.nsplit, slots_cap, minc, knobs.ipw, n_active_max, R);
                 if (!R.n_active) break;
-                for (size_t q = 0; q < R.items.size(); q += 4) {            // every item starts from poisoned scratch + LDS
-                    E.g = &K.gaps[R.items[q]];
-                    FigPersist P; persist_of(*E.g, P);
-                    poison();
-                    fig_spec_eval<true>(E, work, P, R.items[q + 1], R.items[q + 2], E.g->capGg);
-                }
-                for (size_t q = 0; q < R.entries.size(); q += 4) {
-                    E.g = &K.gaps[R.entries[q]];
-                    FigPersist P; persist_of(*E.g, P);
-                    poison();
-                    fig_spec_replay(E, work, P, R.entries[q + 1], E.g->capGg);
-                    publish(R.entries[q]);
-                }
+                for (const FigItem &it : R.items) { poison(); fig_item_eval<true>(E, work, it); }      // every item starts from poisoned scratch + LDS
+                for (const FigEntry &en : R.entries) { poison(); fig_item_replay(E, work, en); }
             }
-            for (int gi : ids) {
-                if (gapctl[(size_t)gi * 4] != 2) continue;
-                E.g = &K.gaps[gi];
-                FigPersist P; persist_of(*E.g, P);
-                poison();
-                fig_bind(E, work, P, FIG_BIND_SEQ, 0, E.g->capGg);
-                fig_state_load(E, P);
-                fig_gap_end<true>(E);
-            }
+            for (int gi : ids) if (ctl[gi].status == FIG_GAP_LOOP_DONE) { poison(); fig_item_end<true>(E, work, gi); }
         }
-        counters[1] += E.flops; counters[3] += E.mle_alg; counters[4] += E.mle_exec;
+        counters[FIG_CNT_FLOPS] += E.flops; counters[FIG_CNT_MLE_ALG] += E.mle_alg; counters[FIG_CNT_MLE_EXEC] += E.mle_exec;
     }
     if (probe_reach) return FIG_OK;
-    ctx->stats.place_calls = (int64_t)counters[0]; ctx->stats.alg_flops = (double)counters[1];
-    ctx->stats.spec_flops = (double)counters[1]; ctx->stats.mle_alg_flops = (double)counters[3]; ctx->stats.mle_exec_flops = (double)counters[4];
+    counters[FIG_CNT_SPEC] = counters[FIG_CNT_FLOPS];      // this build reports no speculation overhead
+    fig_stats_from_counters(counters, ctx->stats);
     ctx->stats.packed_bytes = K.packed_bytes(); ctx->stats.n_launches = (int)K.classes.size();
     for (int64_t g = 0; g < ng; g++) { out->filled_len[g] = fl[g]; out->gaptofill[g] = gtf[g]; }
     return fig_compact_results(ng, str.data(), K.str_off.data(), out);
@@ -212,10 +171,10 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
 extern "C" int fig_emu_plan_round(const int *ids, int n_ids, const int32_t *ctl, int capacity, int nsplit, int slots_cap, int minc, double ipw,
                                   int *n_active_max, int *items, int *n_items, int *entries, int *n_entries, int cap_ints, int *chunk) {
     FigRound R;
-    fig_plan_round(std::vector<int>(ids, ids + n_ids), ctl, capacity, nsplit, slots_cap, minc, ipw, *n_active_max, R);
-    if ((int)R.items.size() > cap_ints || (int)R.entries.size() > cap_ints) return -1;
-    std::copy(R.items.begin(), R.items.end(), items); std::copy(R.entries.begin(), R.entries.end(), entries);
-    *n_items = (int)R.items.size() / 4; *n_entries = (int)R.entries.size() / 4; *chunk = R.chunk;
+    fig_plan_round(std::vector<int>(ids, ids + n_ids), (const FigGapCtl *)ctl, capacity, nsplit, slots_cap, minc, ipw, *n_active_max, R);   // (rows of four int32, as FigGapCtl is)
+    if ((int)R.items.size() * 4 > cap_ints || (int)R.entries.size() * 4 > cap_ints) return -1;
+    memcpy(items, R.items.data(), R.items.size() * sizeof(FigItem)); memcpy(entries, R.entries.data(), R.entries.size() * sizeof(FigEntry));
+    *n_items = (int)R.items.size(); *n_entries = (int)R.entries.size(); *chunk = R.chunk;
     return R.n_active;
 }
 
