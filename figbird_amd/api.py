@@ -65,6 +65,14 @@ class FigGapSupport(C.Structure):
 SUP_NONE, SUP_FINAL, SUP_ORIGINAL, SUP_TIEBREAK = 0, 1, 2, 4
 
 
+class FigGapQuality(C.Structure):
+    _fields_ = [("loglik", c_double_p), ("phred", c_u8_p), ("state", c_u8_p)]
+
+
+# fig_gap_quality::state (include/figbird_hip.h)
+QUAL_OFF, QUAL_ON = 0, 1
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -74,7 +82,7 @@ class FigStats(C.Structure):
 
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
            "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
-           "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset"]
+           "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality"]
 
 _lib = None
 _host = None
@@ -108,6 +116,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.fig_batch_set_ot_preset.argtypes = [C.c_void_p, c_u8_p]
     if hasattr(lib, "fig_fill_resident_ex"):          # (the CPU emulation of the tests implements the ABI without it)
         lib.fig_fill_resident_ex.argtypes = [C.c_void_p, C.POINTER(FigGapResults), C.POINTER(FigGapSupport)]
+    if hasattr(lib, "fig_batch_quality"):             # (likewise)
+        lib.fig_batch_quality.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigGapQuality)]
     if path is None:
         _lib = lib
     return lib
@@ -132,6 +142,10 @@ def load_host_library() -> C.CDLL:
         _host.fighost_run_ot_presets.argtypes = [C.c_void_p, c_u8_p, c_u8_p]
         _host.fighost_run_write.argtypes = [C.c_void_p, c_i32_p, c_i32_p, c_i64_p, C.c_char_p, c_i32_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
         _host.fighost_run_write_support.argtypes = [C.c_void_p, c_i32_p, c_i64_p, C.c_char_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
+        _host.fighost_quality_tables.argtypes = [C.POINTER(FigModel), c_double_p, c_double_p, c_double_p]
+        _host.fighost_quality_phred.argtypes = [C.c_int64, c_double_p, C.c_char_p, c_u8_p]
+        _host.fighost_quality_gaps_on.argtypes = [C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
+        _host.fighost_run_write_quality.argtypes = [C.c_void_p, c_i32_p, c_i64_p, c_u8_p, c_u8_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -276,6 +290,7 @@ class FillResult:
     draw: Optional[tuple] = None           # (draw_pos, draw_isz, draw_len) planes of fig_gap_results, when requested
     support: Optional[np.ndarray] = None   # int32 [total, 5]: read counts (A, C, G, T, other) behind raw[i], i.e. base x of gap g at str_off[g] + x
     support_origin: Optional[np.ndarray] = None   # int32 [n_gaps]: SUP_* mask (fig_gap_support::origin)
+    quality: Optional[tuple] = None        # (loglik float64 [total, 4], phred uint8 [total], state uint8 [n_gaps]) of fig_gap_quality, indexed like raw
 
     @property
     def filled_bases(self) -> int:
@@ -335,7 +350,41 @@ class Engine:
         self._check(self.lib.fig_fill_resident_ex(self.ctx, C.byref(r), C.byref(s)), "fig_fill_resident_ex")
         return sc, so
 
-    def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False) -> FillResult:
+    def quality(self, res: FillResult, origin: Optional[np.ndarray] = None):
+        """fig_batch_quality of the strings and draw planes in `res` against the resident batch; `origin` is
+        FillResult.support_origin, or None for no origin test.  Returns (loglik [total, 4], phred [total], state [n_gaps]) with
+        total = str_off[n_gaps]: base x of gap g at str_off[g] + x.  The buffers handed to the library start as 0xFF bytes, so
+        that an element it failed to write shows."""
+        if not hasattr(self.lib, "fig_batch_quality"):
+            raise RuntimeError("quality needs fig_batch_quality, which this library does not export")
+        if res.draw is None:
+            raise ValueError("quality: the fill result carries no draw planes (fill with draw=True)")
+        n = self.n_gaps
+        fl = np.ascontiguousarray(res.filled_len, dtype=np.int32); so = np.ascontiguousarray(res.str_off, dtype=np.int64)
+        if len(fl) < n or len(so) < n + 1:
+            raise ValueError("quality: one length and one offset per gap of the resident batch")
+        fl = fl if n else np.zeros(1, dtype=np.int32)
+        total = int(so[n])
+        raw = np.ascontiguousarray(res.raw, dtype=np.uint8) if res.raw is not None and len(res.raw) else np.zeros(1, dtype=np.uint8)
+        dpos, disz, dlen = (np.ascontiguousarray(a, dtype=np.int32) for a in res.draw)
+        dpos, disz, dlen = (a if len(a) else np.zeros(1, dtype=np.int32) for a in (dpos, disz, dlen))
+        r = FigGapResults()
+        r.filled_len = _p(fl, c_i32_p); r.str_off = _p(so, c_i64_p); r.str = C.cast(raw.ctypes.data, C.c_char_p); r.str_capacity = len(raw)
+        r.draw_pos = _p(dpos, c_i32_p); r.draw_isz = _p(disz, c_i32_p); r.draw_len = _p(dlen, c_i32_p)
+        org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+        if org is not None and len(org) < n:
+            raise ValueError("quality: one origin per gap of the resident batch")
+        ll = np.full((max(total, 1), 4), np.nan); ll.view(np.uint8)[...] = 0xFF
+        ph = np.full(max(total, 1), 0xFF, dtype=np.uint8); stt = np.full(max(n, 1), 0xFF, dtype=np.uint8)
+        gq = FigGapQuality(); gq.loglik = _p(ll, c_double_p); gq.phred = _p(ph, c_u8_p); gq.state = _p(stt, c_u8_p)
+        self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), None if org is None or not len(org) else _p(org, c_i32_p), C.byref(gq)), "fig_batch_quality")
+        return ll[:total], ph[:total], stt[:n]
+
+    def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False) -> FillResult:
+        """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins)."""
+        if quality and not hasattr(self.lib, "fig_batch_quality"):
+            raise RuntimeError("quality=True needs fig_batch_quality, which this library does not export")
+        draw = draw or quality; support = support or quality
         n = self.n_gaps
         fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
         so = np.zeros(n + 1, dtype=np.int64); st = np.zeros(max(self.cap, 1), dtype=np.uint8)
@@ -378,6 +427,8 @@ class Engine:
             res.draw = (dpos[:nr], disz[:nr], dlen[:2 * n])
         if support:
             res.support = sup_c[:int(so[n])]; res.support_origin = sup_o[:n]
+        if quality:
+            res.quality = self.quality(res, res.support_origin)
         return res
 
     def free_batch(self):
@@ -406,11 +457,18 @@ class Engine:
         if self.n_gaps > 0:
             self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
 
-    def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False) -> FillResult:
+    def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False, quality: bool = False,
+                    keep_resident: bool = False) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
         resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
-        read support as well (fields `support`, `support_origin`)."""
+        read support as well (fields `support`, `support_origin`).  quality=True implies draw and support and runs
+        fig_batch_quality before the batch is freed (field `quality`).  keep_resident=True leaves an uploaded batch resident
+        for a further call."""
+        if quality and not hasattr(self.lib, "fig_batch_quality"):
+            raise RuntimeError("quality=True needs fig_batch_quality, which this library does not export")
+        draw = draw or quality; support = support or quality
+        qual = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
@@ -432,8 +490,12 @@ class Engine:
         if n > 0 and resident:
             try:
                 sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
+                if quality:
+                    self.n_gaps = n
+                    qual = self.quality(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen)), sup_o)
             finally:
-                self.lib.fig_batch_free(self.ctx)
+                if not keep_resident:
+                    self.lib.fig_batch_free(self.ctx)
         elif n > 0:
             self._check(self.lib.fig_fill_gaps(self.ctx, C.byref(cbatch), C.byref(r)), "fig_fill_gaps")
         res = FillResult(fl[:n].copy(), gt[:n].copy(), None, None, str_off=so, raw=st)
@@ -441,12 +503,14 @@ class Engine:
         if support:
             res.support = sup_c[:int(so[n])] if sup_c is not None else np.zeros((0, 5), dtype=np.int32)
             res.support_origin = sup_o[:n] if sup_o is not None else np.zeros(0, dtype=np.int32)
+        if quality:
+            res.quality = qual if qual is not None else (np.zeros((0, 4)), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
         return res
 
-    def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False) -> FillResult:
+    def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality)
         finally:
             self.free_batch()
 

@@ -20,6 +20,8 @@
 #include "fig_engine.h"
 #include "fig_pack.h"
 #include "fig_abi_host.h"
+#include "fig_quality.h"
+#include "fig_quality_host.h"
 
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
@@ -631,6 +633,81 @@ extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fi
     int rc = fig_compact_results(ng, hstr.data(), ctx->h_str_off.data(), out);
     if (!rc && sup) fig_compact_support(ng, hsup.data(), ctx->h_str_off.data(), out, sup->counts);
     return rc;
+}
+
+// Per-base quality of a fill's strings (fig_quality.h: the kernel; fig_quality_host.h: tables, Phred, which gaps are on).  Beside
+// the fill: per-call device buffers, the library's stream, nothing of the resident batch or the model is written.
+extern "C" int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_quality *q) {
+    if (!ctx || !f || !q || !ctx->have_batch || !ctx->have_model) return FIG_EINVAL;
+    if (!f->filled_len || !f->str_off || !f->draw_pos || !f->draw_isz || !f->draw_len || !q->loglik || !q->phred || !q->state) return FIG_EINVAL;
+    hipSetDevice(ctx->device);
+    const int64_t ng = ctx->n_gaps, nr = ctx->n_ureads + ctx->n_preads;
+    if (f->str_off[0] < 0) return FIG_EINVAL;
+    for (int64_t g = 0; g < ng; g++) if (f->str_off[g + 1] < f->str_off[g]) return FIG_EINVAL;
+    const int64_t total = f->str_off[ng];
+    if (total > 0 && !f->str) return FIG_EINVAL;
+    const FigDevBatch &db = ctx->db;
+    const int L = ctx->dm.L;
+    // the gap descriptors (read ranges) and the model's e[k] / 1 - e[k] as the device holds them
+    std::vector<FigDevGap> hg((size_t)ng);
+    std::vector<double> he((size_t)L), home((size_t)L), tabs((size_t)fig_quality_tab_doubles(L));
+    if (ng > 0) FIG_HIP(hipMemcpyAsync(hg.data(), db.gaps, (size_t)ng * sizeof(FigDevGap), hipMemcpyDeviceToHost, ctx->stream));
+    FIG_HIP(hipMemcpyAsync(he.data(), ctx->dm.e, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FIG_HIP(hipMemcpyAsync(home.data(), ctx->dm.ome1, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FIG_HIP(hipStreamSynchronize(ctx->stream));
+    fig_quality_tables(L, he.data(), home.data(), ctx->dm.T, tabs.data(), tabs.data() + L, tabs.data() + 2 * L);
+    // which gaps are on, and the bounds of what the kernel will index with
+    std::vector<int32_t> list, ncol((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<uint8_t> part((size_t)std::max<int64_t>(ng, 1), 0);
+    int64_t cols = 0, reads = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        const int32_t n = f->filled_len[g], lu = f->draw_len[2 * g], lp = f->draw_len[2 * g + 1];
+        q->state[g] = fig_quality_gap_on(n, lu, lp, origin != nullptr, origin ? origin[g] : 0);
+        if (q->state[g] != FIG_QUAL_ON) continue;
+        if (n > (1 << 30) || f->str_off[g] + n > f->str_off[g + 1]) return FIG_EINVAL;
+        const bool p = lp >= 0;
+        const int64_t base = p ? ctx->n_ureads + hg[(size_t)g].pBase : hg[(size_t)g].uBase, cnt = p ? hg[(size_t)g].nP : hg[(size_t)g].nU;
+        if (base < 0 || cnt < 0 || base + cnt > nr) return FIG_EINVAL;
+        const int64_t drawn = fig_quality_check_placements(f->draw_pos + base, cnt);
+        if (drawn < 0) return FIG_EINVAL;
+        list.push_back((int32_t)g); ncol[(size_t)g] = n; part[(size_t)g] = p ? 1 : 0;
+        cols += n; reads += drawn;
+    }
+    float ms = 0;
+    if (total > 0) memset(q->loglik, 0, (size_t)total * 4 * sizeof(double));
+    if (total > 0) memset(q->phred, 0, (size_t)total);
+    if (!list.empty()) {
+        FigTmpBufs tmp;
+        auto up = [&](const void *src, size_t bytes) -> void * {
+            void *p = tmp.alloc(bytes);
+            if (p && bytes && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
+            return p;
+        };
+        FigQualArgs A;
+        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.p_len = db.p.len; A.u_woff = db.u.woff; A.p_woff = db.p.woff;
+        A.packed = db.packed; A.n_ureads = ctx->n_ureads; A.L = L;
+        A.draw_pos = (const int32_t *)up(f->draw_pos, (size_t)nr * 4);
+        A.list = (const int32_t *)up(list.data(), list.size() * 4);
+        A.ncol = (const int32_t *)up(ncol.data(), (size_t)ng * 4);
+        A.partial = (const uint8_t *)up(part.data(), (size_t)ng);
+        A.str_off = (const int64_t *)up(f->str_off, (size_t)(ng + 1) * 8);
+        A.tabs = (const double *)up(tabs.data(), tabs.size() * sizeof(double));
+        A.loglik = (double *)tmp.alloc((size_t)total * 4 * sizeof(double));
+        if (!A.draw_pos || !A.list || !A.ncol || !A.partial || !A.str_off || !A.tabs || !A.loglik) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
+        FIG_HIP(hipMemsetAsync(A.loglik, 0, (size_t)total * 4 * sizeof(double), ctx->stream));
+        FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        hipLaunchKernelGGL(fig_quality_kernel, dim3((unsigned)list.size()), dim3(FIG_Q_NT), 0, ctx->stream, A);
+        FIG_HIP(hipGetLastError());
+        FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        FIG_HIP(hipMemcpyAsync(q->loglik, A.loglik, (size_t)total * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        FIG_HIP(hipStreamSynchronize(ctx->stream));
+        FIG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    }
+    for (int32_t g : list)
+        for (int64_t i = f->str_off[g], e = f->str_off[g] + ncol[(size_t)g]; i < e; i++) q->phred[i] = fig_quality_phred(q->loglik + i * 4, f->str[i]);
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figqual] gaps on %zu of %lld, columns %lld, reads %lld, kernel %.3f ms\n", list.size(), (long long)ng, (long long)cols, (long long)reads, ms);
+    return FIG_OK;
 }
 
 extern "C" int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) { return fig_fill_gaps_once(ctx, batch, out); }

@@ -2,6 +2,7 @@
 // FillGaps.cpp, Preprocess.cpp); behaviour (including quirks) is kept.
 #include "fig_host.h"
 #include "../fig_gaprules.h"
+#include "../fig_quality_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -749,6 +750,20 @@ bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::stri
     return true;
 }
 
+bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+    FILE *f = fopen((a.tmp + "gapquality.txt").c_str(), "w");
+    if (!f) { err = "can't write gapquality.txt"; return false; }
+    std::string Q;
+    for (size_t g = 0; g < b.gap_contig.size(); g++) {
+        const int n = r.filled_len[g];
+        Q.clear();
+        for (int x = 0; x < n; x++) Q += (char)(33 + r.qual_phred[(size_t)r.str_off[g] + x]);
+        fprintf(f, "%d\t%d\t%ld\t%d\t%d\t%d\t%s\n", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g], n, (int)r.qual_state[g], Q.c_str());
+    }
+    fclose(f);
+    return true;
+}
+
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     FILE *f = fopen((a.tmp + "draw.txt").c_str(), "w");
     if (!f) { err = "can't write draw.txt"; return false; }
@@ -1045,5 +1060,40 @@ extern "C" int fighost_run_write_support(void *h, const int32_t *filled_len, con
     R.sup_origin.assign(sup_origin, sup_origin + ng);
     std::string e;
     if (!fighost::write_support(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
+    return 0;
+}
+
+// ------------------------------------------------------------------ per-base quality (fig_quality_host.h)
+// lm[L], le[L], lt[16] of the model, as fig_batch_quality builds them
+extern "C" int fighost_quality_tables(const fig_model *m, double *lm, double *le, double *lt16) {
+    if (!m || !m->error_pos_dist || !lm || !le || !lt16 || m->max_read_length <= 0) return -1;
+    fig_quality_tables_model(m, lm, le, lt16);
+    return 0;
+}
+
+// Phred of `n` columns: loglik [n*4], the emitted bytes str [n] -> phred [n]
+extern "C" int fighost_quality_phred(int64_t n, const double *loglik, const char *str, uint8_t *phred) {
+    for (int64_t i = 0; i < n; i++) phred[i] = fig_quality_phred(loglik + i * 4, str[i]);
+    return 0;
+}
+
+// FIG_QUAL_* of `ng` gaps from their string lengths, draw headers [ng*2] and origins (NULL = no origin test) -> state [ng]
+extern "C" int fighost_quality_gaps_on(int64_t ng, const int32_t *filled_len, const int32_t *draw_len, const int32_t *origin, uint8_t *state) {
+    for (int64_t g = 0; g < ng; g++) state[g] = fig_quality_gap_on(filled_len[g], draw_len[2 * g], draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+    return 0;
+}
+
+// gapquality.txt of the WHOLE gap set (FIGFILL_QUALITY=1): phred [str_off[n_gaps]] indexed like the strings, state [n_gaps]
+extern "C" int fighost_run_write_quality(void *h, const int32_t *filled_len, const int64_t *str_off, const uint8_t *phred, const uint8_t *state,
+                                         char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size();
+    fighost::Results R;
+    R.filled_len.assign(filled_len, filled_len + ng);
+    R.str_off.assign(str_off, str_off + ng + 1);
+    R.qual_phred.assign(phred, phred + (size_t)str_off[ng]);
+    R.qual_state.assign(state, state + ng);
+    std::string e;
+    if (!fighost::write_quality(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
     return 0;
 }

@@ -88,6 +88,8 @@ struct Results {
     std::string str;
     // per-base read support (fig_gap_support), when asked for: [str.size()*5] indexed like str, and [n_gaps]
     std::vector<int32_t> sup_counts, sup_origin;
+    // per-base quality (fig_gap_quality), when asked for: Phred [str.size()] indexed like str, and FIG_QUAL_* [n_gaps]
+    std::vector<uint8_t> qual_phred, qual_state;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
@@ -96,6 +98,9 @@ bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string 
 // gapsupport.txt (no counterpart in the reference): per gap `g contig start G0 n origin S D`, tab-separated, S = n
 // comma-separated supports of the called base (0 under an N), D = n comma-separated depths (sum of the five counts)
 bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gapquality.txt (no counterpart in the reference): per gap `g contig start G0 n state Q`, tab-separated, the first five fields
+// as in gapout.txt, state = FIG_QUAL_*, Q = n characters of Phred+33 (empty for n <= 0)
+bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // filledContigs.fa + Ncount.txt (FillGaps.cpp:708-926)
 bool write_scaffold(const RunArgs &a, const Scaffold &sc, const Batch &b, const Results &r, std::string &err);
 

@@ -23,8 +23,22 @@ using namespace fighost;
 // implements the calls it was written against): bound weakly, and asking for the support plane without it is an error.
 extern "C" int fig_fill_resident_ex(fig_ctx *, fig_gap_results *, const fig_gap_support *) __attribute__((weak));
 
+// fig_batch_quality likewise: FIGFILL_QUALITY=1 on a library without it is an error before anything is filled or written.
+extern "C" int fig_batch_quality(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_quality *) __attribute__((weak));
+
 // FIGFILL_SUPPORT=1: also ask for the per-base read support and write <tmp>/gapsupport.txt
 static bool want_support() { const char *s = getenv("FIGFILL_SUPPORT"); return s && atoi(s) == 1; }
+
+// FIGFILL_QUALITY=1: the fill with the support call (for the origins), then fig_batch_quality, and <tmp>/gapquality.txt
+static bool want_quality() { const char *s = getenv("FIGFILL_QUALITY"); return s && atoi(s) == 1; }
+
+// the per-base quality of the fill `fr` just returned (the batch still resident): R.qual_phred / R.qual_state
+static int quality_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng) {
+    R.qual_phred.assign((size_t)std::max<int64_t>(fr->str_capacity, 1), 0); R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<double> ll((size_t)std::max<int64_t>(fr->str_off[ng], 1) * 4, 0.0);
+    fig_gap_quality gq; gq.loglik = ll.data(); gq.phred = R.qual_phred.data(); gq.state = R.qual_state.data();
+    return fig_batch_quality(ctx, fr, R.sup_origin.data(), &gq);
+}
 
 // the fill, with R.sup_counts / R.sup_origin sized and filled when `support`
 static int fill_resident(fig_ctx *ctx, fig_gap_results *fr, Results &R, int64_t ng, bool support) {
@@ -79,9 +93,10 @@ static void shard_fill(int device, const fig_model *fm, const Scaffold *sc, Shar
     fr.filled_len = R.filled_len.data(); fr.gaptofill = R.gaptofill.data(); fr.str_off = R.str_off.data();
     fr.str = &R.str[0]; fr.str_capacity = (int64_t)R.str.size();
     fr.draw_pos = R.draw_pos.data(); fr.draw_isz = R.draw_isz.data(); fr.draw_len = R.draw_len.data();
-    rc = fill_resident(S->ctx, &fr, R, ng, want_support());
+    rc = fill_resident(S->ctx, &fr, R, ng, want_support() || want_quality());
     fig_get_stats(S->ctx, &S->st);
     if (rc) return shard_fail(S, rc, std::string("fig_fill_resident on device ") + std::to_string(device));
+    if (want_quality() && (rc = quality_resident(S->ctx, &fr, R, ng))) return shard_fail(S, rc, std::string("fig_batch_quality on device ") + std::to_string(device));
     fig_ctx_destroy(S->ctx); S->ctx = nullptr;
 }
 
@@ -123,8 +138,9 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         st.n_launches += runs[r].st.n_launches;
     }
     R.str.clear();
-    const bool support = want_support();
+    const bool support = want_support() || want_quality(), quality = want_quality();
     if (support) R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    if (quality) R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
     for (int64_t g = 0; g < ng; g++) {
         const ShardRun &S = runs[owner[g]]; const int64_t k = local[g];
         R.filled_len[g] = S.R.filled_len[k]; R.gaptofill[g] = S.R.gaptofill[k];
@@ -133,6 +149,10 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         if (support) {                                    // the plane travels with the string: five counts per byte
             R.sup_counts.insert(R.sup_counts.end(), S.R.sup_counts.begin() + S.R.str_off[k] * 5, S.R.sup_counts.begin() + S.R.str_off[k + 1] * 5);
             R.sup_origin[g] = S.R.sup_origin[k];
+        }
+        if (quality) {                                    // and so does the Phred: one byte per string byte
+            R.qual_phred.insert(R.qual_phred.end(), S.R.qual_phred.begin() + S.R.str_off[k], S.R.qual_phred.begin() + S.R.str_off[k + 1]);
+            R.qual_state[g] = S.R.qual_state[k];
         }
         R.draw_len[2 * g] = S.R.draw_len[2 * k]; R.draw_len[2 * g + 1] = S.R.draw_len[2 * k + 1];
         const int64_t nu = B.u_read_off[g + 1] - B.u_read_off[g], np = B.p_read_off[g + 1] - B.p_read_off[g];
@@ -143,6 +163,7 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
     R.str_off[ng] = (int64_t)R.str.size();
     if (R.str.empty()) R.str.assign(1, 'N');
     if (support && R.sup_counts.empty()) R.sup_counts.assign(5, 0);
+    if (quality && R.qual_phred.empty()) R.qual_phred.assign(1, 0);
     return 0;
 }
 
@@ -173,6 +194,7 @@ int main(int argc, char **argv) {
         }
         if (devices.empty()) return fail("figfill: FIGFILL_DEVICES must be a comma-separated list of GPU ordinals");
     }
+    if (want_quality() && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
     setenv("GPU_MAX_HW_QUEUES", "8", 0);                 // one hardware queue per scheduler lane; before any thread or HIP call (fig_abi.hip: fig_ctx_create)
     auto t0 = std::chrono::steady_clock::now();
 
@@ -215,6 +237,7 @@ int main(int argc, char **argv) {
         if (!write_gaploads(a, B, err)) return fail(err);
         if (!write_scaffold(a, sc, B, R, err)) return fail(err);
         if (want_support() && !write_support(a, B, R, err)) return fail(err);
+        if (want_quality() && !write_quality(a, B, R, err)) return fail(err);
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         printf("Time taken = %g seconds (%zu GPUs; slowest shard's device kernels %.3f ms, %lld placeReads calls)\n", secs, devices.size(), st.kernel_ms, (long long)st.place_calls);
         printf("======================================\n");
@@ -255,16 +278,20 @@ int main(int argc, char **argv) {
         rc = fig_batch_probe_reach(ctx, reach.data());
         if (!rc) { ot_presets_from_reach(B, reach.data()); rc = fig_batch_set_ot_preset(ctx, B.gap_ot_preset.data()); }
     }
-    if (!rc) rc = fill_resident(ctx, &fr, R, ng, want_support());
+    if (!rc) rc = fill_resident(ctx, &fr, R, ng, want_support() || want_quality());
     fig_stats st; memset(&st, 0, sizeof(st)); fig_get_stats(ctx, &st);
+    int qrc = 0;
+    if (!rc && want_quality()) qrc = quality_resident(ctx, &fr, R, ng);
     fig_ctx_destroy(ctx);
     if (rc) return fail(std::string("figfill: fill: ") + fig_strerror(rc));
+    if (qrc) return fail(std::string("figfill: fig_batch_quality: ") + fig_strerror(qrc));
 
     if (!write_gapout(a, B, R, err)) return fail(err);
     if (!write_draw(a, B, R, err)) return fail(err);
     if (!write_gaploads(a, B, err)) return fail(err);
     if (!write_scaffold(a, sc, B, R, err)) return fail(err);
     if (want_support() && !write_support(a, B, R, err)) return fail(err);
+    if (want_quality() && !write_quality(a, B, R, err)) return fail(err);
     if (trace) {
         FILE *f = fopen(trace, "w");
         if (f) {

@@ -36,6 +36,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     # FIGFILL_SUPPORT=1: also gapsupport.txt, the per-base read support (fig_gap_support); read as figfill reads it, atoi(s) == 1
     m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_SUPPORT", ""))
     support = m is not None and int(m.group(0)) == 1
+    # FIGFILL_QUALITY=1: also gapquality.txt, the per-base Phred (fig_gap_quality); the fill then runs with the support call
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_QUALITY", ""))
+    quality = m is not None and int(m.group(0)) == 1
     own_pg = False
     if world > 1 and not dist.is_initialized():
         be = backend or ("nccl" if torch.cuda.is_available() else "gloo")
@@ -99,7 +102,7 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
             preset = np.zeros(max(n, 1), dtype=np.uint8)
             host.fighost_run_ot_presets(h, api._p(reach, api.c_u8_p), api._p(preset, api.c_u8_p))
             eng.set_ot_preset(preset[mine] if len(mine) else np.zeros(0, dtype=np.uint8))
-            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support)
+            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality, quality=quality)
             st = eng.stats()
             eng.close()
         except Exception as e:
@@ -117,7 +120,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
         dpos, disz, dlen = res.draw
         # the support plane travels as two more extras: the shard's counts, five per string byte in shard order, and its origins
         sup_x = [res.support.reshape(-1), res.support_origin] if support else []
-        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz] + sup_x)
+        # and so does the quality: the shard's Phred, one per string byte in shard order, and its states (widened to the extras' int32)
+        qual_x = [res.quality[1].astype(np.int32), res.quality[2].astype(np.int32)] if quality else []
+        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz] + sup_x + qual_x)
         wrc = 0
         try:
             fl, gt, ps, per_rank = out
@@ -128,16 +133,22 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 g_pos = np.full(max(NU + NP, 1), np.iinfo(np.int32).min, dtype=np.int32); g_isz = np.zeros(max(NU + NP, 1), dtype=np.int32)
                 g_len = np.full(max(2 * n, 1), -1, dtype=np.int32)
                 g_sup = np.zeros((max(int(ps.off[-1]), 1), 5), dtype=np.int32); g_org = np.zeros(max(n, 1), dtype=np.int32)
-                for ids, r_len, r_pos, r_isz, *r_sup in per_rank:
+                g_phr = np.zeros(max(int(ps.off[-1]), 1), dtype=np.uint8); g_qst = np.zeros(max(n, 1), dtype=np.uint8)
+                for ids, r_len, r_pos, r_isz, *r_x in per_rank:
                     ids = np.asarray(ids, dtype=np.int64)
                     if len(ids) == 0:
                         continue
-                    if support:      # a shard's strings lie back to back in its own gap order; ps.off is the global layout
+                    r_sup, r_qual = (r_x[:2], r_x[2:]) if support else ([], r_x)
+                    if support or quality:      # a shard's strings lie back to back in its own gap order; ps.off is the global layout
                         ln = np.maximum(fl[ids], 0).astype(np.int64)
                         src0 = np.cumsum(ln) - ln
                         idx = np.repeat(ps.off[ids] - src0, ln) + np.arange(int(ln.sum()), dtype=np.int64)
+                    if support:
                         g_sup[idx] = r_sup[0].reshape(-1, 5)[:int(ln.sum())]
                         g_org[ids] = r_sup[1]
+                    if quality:
+                        g_phr[idx] = r_qual[0][:int(ln.sum())]
+                        g_qst[ids] = r_qual[1]
                     g_len[2 * ids] = r_len[0::2]; g_len[2 * ids + 1] = r_len[1::2]
                     cu = nu[ids]; cp = npp[ids]
                     su_ = int(cu.sum())
@@ -155,6 +166,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 if wrc == 0 and support:
                     wrc = host.fighost_run_write_support(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
                                                          C.cast(raw.ctypes.data, C.c_char_p), api._p(g_sup, api.c_i32_p), api._p(g_org, api.c_i32_p), err, 512)
+                if wrc == 0 and quality:
+                    wrc = host.fighost_run_write_quality(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
+                                                         api._p(g_phr, api.c_u8_p), api._p(g_qst, api.c_u8_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

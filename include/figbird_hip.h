@@ -151,6 +151,38 @@ typedef struct fig_gap_support {
     int32_t *origin;                    /* [n_gaps] FIG_SUP_* mask                                                      */
 } fig_gap_support;
 
+/* Optional per-base quality of the filled bases (fig_batch_quality): how likely each emitted base is wrong, under the run's own
+ * error model -- errorPosDist[k] (index len-1-j for base j of an unmapped read whose is_reverse bit is set, Figbird.cpp:3569-3576;
+ * j for every other read) and errorTypeProbs[from][to], the tables the E-step weighs placements with.
+ *
+ * Evidence of a gap = that of its support plane: the reads its draw header lists, each at its drawn offset o, base j of the read
+ * on column x = o + j for 0 <= x < n = filled_len[g].  draw_len[2g] >= 0: the gap's unmapped reads; draw_len[2g+1] >= 0: its
+ * partial reads (never both).  A read whose draw_pos is INT32_MIN and read bases outside ACGT take no part.
+ *
+ * Tables, built on the host with the C library's log10 (log10(0) = -inf is kept): lm[k] = log10(1 - e[k]),
+ * le[k] = log10(e[k]), lt[b][s] = log10(errorTypeProbs[b*5+s]) with b the true base and s the read base, both in A..T.
+ * Column log-likelihoods: for true base b and read base s the term is lm[k] if s == b, else le[k] + lt[b][s];
+ * LL[x][b] = LL[x][b] + term, from 0.0, the reads of the gap in ascending read index, every + one IEEE double addition.  The
+ * device only adds table entries in that order, so the plane is reproducible bit for bit from the tables.
+ *
+ * Phred of a column with emitted byte c: 0 if c is not one of ACGT; m = max LL, 0 if m == -inf; w[b] = pow(10, LL[b] - m)
+ * (-inf gives 0); num = sum of w[b], b != c, in the order A, C, G, T; perr = num / (num + w[c]); 93 if perr == 0, else
+ * floor(-10*log10(perr) + 0.5) clamped to 0..93.
+ *
+ * A gap is FIG_QUAL_ON iff n > 0, exactly one of its two draw_len entries is >= 0 and equals n, and -- when origins are given --
+ * its origin has FIG_SUP_FINAL and lacks FIG_SUP_ORIGINAL (FIG_SUP_TIEBREAK does not matter).  Every other gap is FIG_QUAL_OFF:
+ * its LL are all 0.0 and its Phred all 0, written by the library whatever the buffers held.
+ *
+ * Limits of the number: reads are taken as independent, the placement is taken as given, and the prior over bases is uniform.
+ * It is therefore an UPPER bound on confidence.  A masked 'N' has quality 0 even where its column has support. */
+#define FIG_QUAL_OFF 0
+#define FIG_QUAL_ON  1
+typedef struct fig_gap_quality {
+    double  *loglik;   /* [str_off[n_gaps]*4], base x of gap g at (str_off[g]+x)*4 + b */
+    uint8_t *phred;    /* [str_off[n_gaps]]   */
+    uint8_t *state;    /* [n_gaps] FIG_QUAL_* */
+} fig_gap_quality;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -195,6 +227,14 @@ int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out
  * fig_batch_set_ot_preset: replaces gap_ot_preset of the resident batch ([n_gaps], batch order). */
 int fig_batch_probe_reach(fig_ctx *ctx, uint8_t *reach);
 int fig_batch_set_ot_preset(fig_ctx *ctx, const uint8_t *preset);
+
+/* Per-base quality of the strings in `filled` against the RESIDENT batch (see fig_gap_quality).  `filled` holds what a fill of that
+ * batch returned, or what a caller made by hand: filled_len, str_off, str and the three draw planes.  origin is
+ * fig_gap_support::origin, or NULL for no origin test.  Reads the resident batch and the model and writes neither: a
+ * fig_fill_resident after it gives the bytes it gave before.  FIG_EINVAL without a resident batch, with a needed pointer NULL,
+ * with str_off not leaving filled_len[g] bytes to gap g, or with a drawn offset |o| >= 2^20 in a gap that is on.  With
+ * FIG_SCHED_LOG set, one "[figqual]" line on stderr: gaps on, columns, reads, HIP-event milliseconds of the kernel. */
+int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, fig_gap_quality *q);
 
 int fig_get_stats(const fig_ctx *ctx, fig_stats *out);
 
