@@ -126,6 +126,9 @@ FIG_D void fig_mblk_compute_r(const FigMBlk &B, int a, int b, double &qa, double
 // log + pow.  tools/ubench/pweights_check.c runs the same operations on the host: against glibc on 2e7 arguments over
 // [2^-1070, 1], ln p is equal on 99.56 % (max 1 ulp) and 10^t is within 1 ulp wherever ln p is equal (a 1-ulp difference
 // in t moves w by up to ~10^3 ulp whatever computes it: pow's sensitivity).  Exact for p = 0 (-inf, 0) and p = 1 (0, 1).
+// Measured ON THE DEVICE (tools/probe/fig_mathprobe.hip calls this very function; tests/test_device_math.py, 30 403 arguments
+// over [2^-1070, 1]) against mpmath: ln p within 0.9985 ulp (none above 1 ulp), 10^t within 1.0 ulp of the exact power AT THE
+// ROUNDED t the function returns (none above 1 ulp); p = 0 -> (-inf, 0) and p = 1 -> (0, 1) exactly.  The test holds both to 2 ulp.
 template <int N>
 FIG_D void fig_pweights(const double (&x)[N], double (&t)[N], double (&w)[N]) {
 #ifdef FIG_EMU

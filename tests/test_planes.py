@@ -2,6 +2,7 @@
 as the last E-step left it and the per-read E-step maxima (maxlikelihood_value), exported through the C ABI's debug
 planes and compared with the oracle's level-3 trace.  Tolerance 1e-6 relative (device libm vs glibc differ in the last
 ulp; the emulation build uses glibc and the reference's summation order, so it must be exact); 0 and +-inf exact."""
+import json
 import os
 
 import numpy as np
@@ -35,17 +36,28 @@ def _close(a, b, tol):
     return bool(ok.all()), (int(np.argmin(ok)) if not ok.all() else -1)
 
 
-def check_planes(lib_path, name, tmp_path, tol):
-    from tools.make_golden import make
-    root = util.extract_golden(name, str(tmp_path))
-    tr = str(tmp_path / "o.trace")
-    assert util.run_oracle_fillgaps(root, trace=tr, level=3).returncode == 0
-    planes = parse_planes(tr)
-    case = make(name)
+def prepare(src, tmp_path):
+    """A fill golden's name or a synth.Case -> (root directory with the written inputs and a meta.json, the Case)."""
+    if isinstance(src, str):
+        from tools.make_golden import make
+        return util.extract_golden(src, str(tmp_path)), make(src)
+    root = os.path.join(str(tmp_path), src.name)
+    synth.write_case(src, root)
+    rel = {"scf": "scf.fa", "myout": "tmp/myout.sam", "tmp": "tmp/", "gaps": "gaps/"}
+    with open(os.path.join(root, "meta.json"), "w") as f:
+        json.dump({"name": src.name, "n_gaps": len(src.gaps), "figbird_argv": synth.figbird_argv(src, rel), "fillgaps_argv": synth.fillgaps_argv(src, rel)}, f)
+    return root, src
+
+
+def model_of(root):
     a = util.meta(root)["fillgaps_argv"]
-    model = api.model_from_files(os.path.join(root, "scf.fa"), os.path.join(root, "tmp") + "/", os.path.join(root, "tmp", "myout.sam"),
-                                 partial_flag=int(a[4]), unmapped_flag=int(a[5]), script_itr=int(a[3]), max_distance=int(a[1]),
-                                 read_length=int(a[2]), neg_overlap=int(a[10]), partial_len=int(a[11]))
+    return api.model_from_files(os.path.join(root, "scf.fa"), os.path.join(root, "tmp") + "/", os.path.join(root, "tmp", "myout.sam"),
+                                partial_flag=int(a[4]), unmapped_flag=int(a[5]), script_itr=int(a[3]), max_distance=int(a[1]),
+                                read_length=int(a[2]), neg_overlap=int(a[10]), partial_len=int(a[11]))
+
+
+def fill_with_planes(lib_path, case, model, planes):
+    """Fill through the C ABI with the candidate records and both planes on -> (FillResult, fig_get_stats)."""
     batch = synth.case_to_batch(case)
     off = batch.u_read_off if case.mode == "unmapped" else batch.p_read_off
     cols = int(max(max(G for G, _, _ in v) for v in planes.values())) + 1
@@ -53,7 +65,12 @@ def check_planes(lib_path, name, tmp_path, tol):
     eng = api.Engine(0, lib_path=lib_path)
     eng.set_model(model)
     res = eng.fill(batch, debug_cand=512, plane_cols=cols, plane_reads=reads)
+    st = eng.stats()
     eng.close()
+    return res, st
+
+
+def compare_planes(res, planes, tol):
     n_checked = 0
     for g, recs in planes.items():
         got = res.cand[g]
@@ -69,6 +86,16 @@ def check_planes(lib_path, name, tmp_path, tol):
                 assert ok, f"gap {g} G={G}: read {at}: {res.read_maxlv[g, k, at]!r} vs {rmax[at]!r}"
     assert n_checked > 0
     return n_checked
+
+
+def check_planes(lib_path, src, tmp_path, tol):
+    """src: the name of a fill golden, or a synth.Case (written to tmp_path first)."""
+    root, case = prepare(src, tmp_path)
+    tr = str(tmp_path / "o.trace")
+    assert util.run_oracle_fillgaps(root, trace=tr, level=3).returncode == 0
+    planes = parse_planes(tr)
+    res, _ = fill_with_planes(lib_path, case, model_of(root), planes)
+    return compare_planes(res, planes, tol)
 
 
 @pytest.mark.parametrize("name", ["unmapped_small", "partial_small"])

@@ -40,12 +40,19 @@ CASES = {
     "bench_cap40": dict(g0=40, reads=2990, seed=9004),        # <= 400 bp at the 3000-read cap
     "bench_c1100": dict(g0=1100, reads=700, seed=9005),       # one candidate; 1398 table columns: the one-weight-row LDS class
     "bench_t1800": dict(g0=1800, reads=900, seed=9006),       # one candidate; 2098 columns: the LDS-tiled class
+    # candidates 74..372 in the 256-thread class (longest probe 447 columns): the sweep crosses G + L - 1 = 512 | 513, where
+    # fig_sh_applies (fig_engine_shared.h) hands the E-step from the shared-factor form to the pair form inside ONE gap.  Few
+    # reads and a 900-bp insert keep the 299 candidates affordable for the CPU (tests/test_estep_forms.py).
+    "bench_x149": dict(g0=149, reads=40, seed=9007, insert=(900.0, 90.0), planes=(362, 363, 364, 365)),
 }
 N_PLANE_CANDS = 10
 
 
 def spec_of(c):
-    return synth.BenchSpec(mode="unmapped", reads_per_gap_mean=float(c["reads"]))
+    spec = synth.BenchSpec(mode="unmapped", reads_per_gap_mean=float(c["reads"]))
+    if "insert" in c:
+        spec.insert_mean, spec.insert_sd = c["insert"]
+    return spec
 
 
 def make(name):
@@ -134,7 +141,8 @@ def collect(name):
     stats = [ln for ln in open(os.path.join(base, "orc", "o.trace")) if ln.startswith("STATS")]
     Gs = [c[0] for c in cands if c[0] in planes]
     best = max(cands, key=lambda c: float.fromhex(c[2]))[0] if cands else None
-    pick = sorted(set([Gs[int(round(i * (len(Gs) - 1) / max(1, N_PLANE_CANDS - 1)))] for i in range(min(N_PLANE_CANDS, len(Gs)))] + ([best] if best in planes else [])))
+    pick = sorted(set([Gs[int(round(i * (len(Gs) - 1) / max(1, N_PLANE_CANDS - 1)))] for i in range(min(N_PLANE_CANDS, len(Gs)))] + ([best] if best in planes else []) +
+                      [G for G in CASES[name].get("planes", ()) if G in planes]))
     arrs = {}
     for G in pick:
         e, r = planes[G]
