@@ -202,7 +202,9 @@ def make_case(name: str, seed: int, mode: str, gap_specs: List[Tuple[int, int]],
               neg_overlap_gaps: Optional[dict] = None,
               read_n_rate: float = 0.0,
               max_reads_per_gap: int = 3000,
-              model_indel_rate: float = 0.0) -> Case:
+              model_indel_rate: float = 0.0,
+              partial_n_rate: float = 0.0,
+              partial_n_gaps: Optional[List[int]] = None) -> Case:
     """One scaffold with gaps at `gap_specs` = [(start0_in_truth, true_len), ...].
 
     mode "unmapped": jump library N(insert_mean, insert_sd) -> gaps_<g>.sam (+ frag-library
@@ -211,6 +213,8 @@ def make_case(name: str, seed: int, mode: str, gap_specs: List[Tuple[int, int]],
     mode "partial" : frag library N(insert_mean, insert_sd) -> partial_gaps_<g>.sam only.
     `neg_overlap_gaps` maps gap index -> (n_run_len, overlap): the scaffold carries an
     n_run_len N-run although the flanks really overlap by `overlap` bases.
+    `partial_n_rate` writes N over bases of the soft-clipped reads at that rate (`read_n_rate` does so for the
+    unmapped mates), in the gaps `partial_n_gaps` (default: all); at 0 it draws nothing from the generator.
     """
     rng = np.random.default_rng(np.random.PCG64(seed))
     L = read_len
@@ -240,6 +244,14 @@ def make_case(name: str, seed: int, mode: str, gap_specs: List[Tuple[int, int]],
             cursor = ts + tl
     scaf_parts.append(truth[cursor:])
     scaffold = "".join(scaf_parts)
+
+    def _with_n(seq: str, gi: int) -> str:
+        if partial_n_rate <= 0 or (partial_n_gaps is not None and gi not in partial_n_gaps):
+            return seq
+        b = bytearray(seq.encode())
+        for h in np.nonzero(rng.random(len(b)) < partial_n_rate)[0]:
+            b[h] = ord("N")
+        return b.decode()
 
     def t2s(tpos: int, side: str, gi: int) -> int:
         """truth coordinate -> scaffold coordinate for a base in the flank of gap gi."""
@@ -309,6 +321,7 @@ def make_case(name: str, seed: int, mode: str, gap_specs: List[Tuple[int, int]],
                         if s < 0 or s + L > len(truth):
                             continue
                         seq, _ = _mutate(rng, truth[s:s + L], err)
+                        seq = _with_n(seq, gi)
                         pos1 = t2s(s, "L", gi) + 1
                         clipped_index = g.start - pos1
                         cigar = f"{aligned}M{L - aligned}S"
@@ -331,6 +344,7 @@ def make_case(name: str, seed: int, mode: str, gap_specs: List[Tuple[int, int]],
                             # how a short gap looks; keep it.
                             pass
                         seq, _ = _mutate(rng, truth[s:s + L], err)
+                        seq = _with_n(seq, gi)
                         pos1 = g.start + g.length + 1   # first aligned base after the gap, 1-based
                         clipped_index = clip
                         cigar = f"{clip}S{aligned}M"

@@ -18,7 +18,7 @@
 // Usage (same positional arguments as the reference programs):
 //   figbird_oracle figbird  <16 args of Figbird.cpp main, Figbird.cpp:6957-6973>
 //   figbird_oracle fillgaps <15 args of FillGaps.cpp main, FillGaps.cpp:419-433>
-// Env: FIG_ORACLE_TRACE=<file> FIG_ORACLE_TRACE_LEVEL=1|2|3|4 -> per-candidate / per-iteration
+// Env: FIG_ORACLE_TRACE=<file> FIG_ORACLE_TRACE_LEVEL=1..8 -> per-candidate / per-iteration
 //      numeric planes (hex floats) used as kernel-parity fixtures.
 //      FIG_ORACLE_ULP_JITTER=<seed>[:<k>] -> libm sensitivity audit (see lm_jit below); never set by the parity tests.
 #include <algorithm>
@@ -63,6 +63,11 @@ void trace_plane_flush() {
     fwrite(g_plane_buf, 1, g_plane_len, g_trace);
     free(g_plane_buf); g_plane_buf = nullptr;
 }
+// Trace levels 5..8 = levels 1..4 plus one DET line per partial-mode placeReads call: what detect_overlap_gapestimate returned
+// (ret_val[0], ret_val[1], partial_saved_read_temp[0..1]) and, trace only, how many accepted pairs had the maximal overlap
+// length and whether a false overlap was seen (tools/partial_cases.py: which branch of the detector a fixture reaches).
+int g_trace_det = 0;
+int g_det_nmax = 0, g_det_false = 0;
 long g_place_calls = 0;
 double g_flops = 0;                 // algorithmic FP64 flops: 4 per E-step base, 1 per MLE base, 1 per countsGap add
 

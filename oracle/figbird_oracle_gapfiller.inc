@@ -385,6 +385,7 @@ struct GF {
     // pflag: [k*stride + 0] = used flag, [k*stride + 1] = placed position.
     void detect_overlap_gapestimate(const int *pflag, int stride, int gaplen, int *ret_v, int len_thresh) {
         int l_max = -MAX_GAP, r_min = MAX_GAP;
+        g_det_nmax = 0; g_det_false = 0;                 // trace only
         vector<int> left_cross, right_cross;
         int pc = 0, overlap_count = 0;
         double mismatch_threshold = .1;
@@ -468,7 +469,9 @@ struct GF {
                         if (len1 > 0 && len2 > 0 && len1 == len2) {
                             double mismatch_frac = getDiff(common_left, common_right, len1);
                             if (mismatch_frac <= mismatch_threshold) {
+                                if (len1 == max_overlap) g_det_nmax++;      // trace only
                                 if (len1 > max_overlap) {
+                                    g_det_nmax = 1;
                                     max_overlap = len1;
                                     partial_saved_read_temp[0] = left_cross[i];
                                     partial_saved_read_temp[1] = right_cross[j];
@@ -477,6 +480,7 @@ struct GF {
                         }
                     }
                 }
+            g_det_false = false_overlap_flag;
             if ((false_overlap_flag == 0 && max_overlap >= overlap_threshold) ||
                 (false_overlap_flag == -1 && max_overlap >= 2 * overlap_threshold)) {
                 ret_v[0] = max_overlap; ret_v[1] = 0;
@@ -715,6 +719,9 @@ struct GF {
             if (ret_val[0] == 300) maxLikelihood += ret_val[0];
             else if (ret_val[0] >= 1 && ret_val[0] < MAX_READLENGTH) maxLikelihood += 30 * ret_val[0];
             else if (ret_val[1] == -1) maxLikelihood += -100;
+            if (g_trace && g_trace_det)
+                fprintf(g_trace, "DET\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", g, gapLength, ret_val[0], ret_val[1], partial_saved_read_temp[0],
+                        partial_saved_read_temp[1], g_det_nmax, g_det_false, partial_read_count);
         }
 
         count_of_read = num_reads_in_gap;
@@ -1866,7 +1873,8 @@ static int oracle_main(int argc, char **argv) {
     init_char_codes();
     lm_jit_init();
     const char *tr = getenv("FIG_ORACLE_TRACE");
-    if (tr) { g_trace = fopen(tr, "w"); const char *lv = getenv("FIG_ORACLE_TRACE_LEVEL"); g_trace_level = lv ? atoi(lv) : 1; }
+    if (tr) { g_trace = fopen(tr, "w"); const char *lv = getenv("FIG_ORACLE_TRACE_LEVEL"); g_trace_level = lv ? atoi(lv) : 1;
+              if (g_trace_level >= 5) { g_trace_det = 1; g_trace_level -= 4; } }        // 5..8: levels 1..4 plus the DET lines
     int thread_id = 0, totalgapstofill = 0, num_threads = 1;
     if (mode == "figbird") {
         if (argc < 17) { fprintf(stderr, "figbird mode needs 15-16 args\n"); return 2; }

@@ -265,28 +265,93 @@ def test_partial_mode_bench_shape_properties():
     assert called > 0 and wrong <= 0.01 * called, (called, wrong)
 
 
+def _oracle_compare_partial(batch, res, sample, mc, spec, tmp_path, nproc=4, timeout=1500):
+    """The partial-mode variant of _oracle_compare (argv ... "1", "1", "0", "1" ...: script_itr, partial_flag, unmapped_flag,
+    threads, as synth.fillgaps_argv writes them): the sample's gaps are dealt over `nproc` oracle processes, dearest first, each
+    with its own copy of the inputs; filled_len and string of every sampled gap equal the device's.  -> gaps compared."""
+    import subprocess
+    G, L = np.asarray(batch.gap_len), spec.read_len
+    cost = lambda g: (3 * L if G[g] <= L else 5 * int(G[g]) if G[g] <= 2 * L else 1) * (int(G[g]) + 2 * L)     # candidates x columns
+    order = sorted(sample, key=lambda g: (-cost(g), g))
+    runs = []
+    for i in range(nproc):
+        part = order[i::nproc]
+        if not part:
+            continue
+        paths = synth.write_batch_subset(batch, part, mc, str(tmp_path / f"cpu{i}"), spec)
+        args = [paths["scf"], str(spec.max_distance), str(spec.read_len), "1", "1", "0", "1", paths["myout"], paths["tmp"], paths["gaps"],
+                "30", str(mc.partial_len), "10", "0", str(int(spec.insert_mean))]
+        runs.append((part, paths, subprocess.Popen([util.ORACLE, "fillgaps"] + args, cwd=str(tmp_path), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)))
+    n = 0
+    for part, paths, p in runs:
+        _, err = p.communicate(timeout=timeout)
+        assert p.returncode == 0, err
+        lines = util.read(paths["tmp"] + "gapout.txt").splitlines()
+        for k, g in enumerate(paths["gap_order"]):
+            if g not in part:
+                continue
+            f = lines[k].split("\t")
+            assert int(f[4]) == int(res.filled_len[g]), f"gap {g} (G0={int(G[g])})"
+            assert (f[5] if len(f) > 5 else "") == res.strings[g], f"gap {g} (G0={int(G[g])})"
+            n += 1
+    assert n == len(sample)
+    return n
+
+
+def test_partial_mode_bench_shape_matches_oracle_on_a_sample(tmp_path):
+    """The batch of test_partial_mode_bench_shape_properties (same spec, seed and 512 gaps, so its classes run as split lanes),
+    with 96 of its gaps compared with the oracle byte for byte (filled_len and string): the first 24 in batch order of every
+    length bracket of the GAGE mix (<= 30, 31-133, 134-400, > 400 bp).  A wrong pile-up column, which the property test's
+    1 % against the truth lets through, fails here.  Oracle cost: 33 s of wall time as 4 processes (132 s of CPU; the 102-202-bp
+    gaps, five candidates per base of the gap, dominate)."""
+    spec = synth.BenchSpec(mode="partial", read_len=101, insert_mean=180, insert_sd=10, partial_cov=40)
+    eng, mc = _bench_engine(spec)
+    batch, _ = synth.make_bench_batch(77, 512, spec)
+    res = eng.fill(batch)
+    eng.close()
+    assert _loaded_native()
+    G = np.asarray(batch.gap_len)
+    sample = []
+    for lo, hi in [(1, 31), (31, 134), (134, 401), (401, 1 << 30)]:
+        ids = [g for g in range(batch.n_gaps) if lo <= G[g] < hi]
+        assert len(ids) >= 24
+        sample += ids[:24]
+    assert _oracle_compare_partial(batch, res, sample, mc, spec, tmp_path) == 96
+
+
 def test_scheduler_modes_agree(monkeypatch):
     """The candidate-parallel scheduler (speculative candidates + ordered replay, the default) and the plain
     one-workgroup-per-gap kernel (FIG_SCHED=seq) are the same device arithmetic in a different order of
-    launches: strings, gaptofill, candidate records and likelihoods must be bit-identical."""
+    launches: strings, gaptofill, candidate records and likelihoods must be bit-identical.  So must the planner's
+    other settings be: the class lanes one after the other (FIG_LANES=serial), one candidate per gap and round and one
+    item per workgroup (FIG_MIN_CHUNK=1 FIG_ITEMS_PER_WG=1), and 64 candidates per gap and round (FIG_MIN_CHUNK=64)."""
     spec = synth.BenchSpec(mode="unmapped", reads_per_gap_mean=25.0)
     eng, _ = _bench_engine(spec)
     batch, _ = synth.make_bench_batch(77, 96, spec, gap_lengths=np.array(([3, 12, 31, 40, 90, 160, 420, 1300] * 12)))
     eng.upload(batch)
-    monkeypatch.delenv("FIG_SCHED", raising=False)
+    knobs = ("FIG_SCHED", "FIG_LANES", "FIG_MIN_CHUNK", "FIG_ITEMS_PER_WG")
+    for k in knobs:
+        monkeypatch.delenv(k, raising=False)
     par = eng.fill_resident(debug_cand=64)
-    monkeypatch.setenv("FIG_SCHED", "seq")
-    seq = eng.fill_resident(debug_cand=64)
+    others = {}
+    for name, env in {"seq": {"FIG_SCHED": "seq"}, "lanes_serial": {"FIG_LANES": "serial"}, "chunk1_ipw1": {"FIG_MIN_CHUNK": "1", "FIG_ITEMS_PER_WG": "1"},
+                      "chunk64": {"FIG_MIN_CHUNK": "64"}}.items():
+        for k in knobs:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        others[name] = eng.fill_resident(debug_cand=64)
     eng.free_batch(); eng.close()
-    assert par.strings == seq.strings
-    assert list(par.filled_len) == list(seq.filled_len) and list(par.gaptofill) == list(seq.gaptofill)
-    assert list(par.n_place) == list(seq.n_place)
-    for g in range(batch.n_gaps):
-        a, b = par.cand[g], seq.cand[g]
-        assert len(a) == len(b), f"gap {g}"
-        for x, y in zip(a, b):
-            assert tuple(x[:3]) == tuple(y[:3]), f"gap {g}"
-            assert x[3] == y[3] or (np.isnan(x[3]) and np.isnan(y[3])), f"gap {g}: {x} vs {y}"
+    for name, seq in others.items():
+        assert par.strings == seq.strings, name
+        assert list(par.filled_len) == list(seq.filled_len) and list(par.gaptofill) == list(seq.gaptofill), name
+        assert list(par.n_place) == list(seq.n_place), name
+        for g in range(batch.n_gaps):
+            a, b = par.cand[g], seq.cand[g]
+            assert len(a) == len(b), f"{name}: gap {g}"
+            for x, y in zip(a, b):
+                assert tuple(x[:3]) == tuple(y[:3]), f"{name}: gap {g}"
+                assert x[3] == y[3] or (np.isnan(x[3]) and np.isnan(y[3])), f"{name}: gap {g}: {x} vs {y}"
 
 
 @pytest.mark.parametrize("seed", [531, 532])

@@ -11,6 +11,7 @@ Fixtures are data only (inputs + expected outputs); no reference source is copie
 import os, shutil, subprocess, sys, tarfile, tempfile, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from figbird_amd import synth
+from tools import partial_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref")
@@ -71,6 +72,8 @@ CASES = {
     "unmapped_L31": dict(seed=931, mode="unmapped", gap_specs=[(1500, 12), (2900, 29), (4300, 600)], read_len=31, insert_mean=600, insert_sd=30,
                          coverage=8, err=0.005, n_model_pairs=400, contig_len=6400),
 }
+# ---- partial mode's fallback forms and overlap detector: the directed cases of tools/partial_cases.py (builders, not kwargs)
+DIRECTED = partial_cases.all_cases()
 N_THREADS = {"threads3": 3, "ot_carry_t3": 3}
 SET_INPUTMEAN = {"inputmean": 1}
 
@@ -178,6 +181,8 @@ POST = {"partial_L150": _post_clip_hang, "partial_L199": _post_clip_hang, "ot_ca
 
 def make(name):
     """The Case of a golden fixture, exactly as it was generated (tests rebuild in-memory batches from this)."""
+    if name in DIRECTED:
+        return DIRECTED[name]()
     kw = dict(CASES[name])
     case = synth.make_case(name, kw.pop("seed"), kw.pop("mode"), kw.pop("gap_specs"), **kw)
     if name in POST:
@@ -225,7 +230,7 @@ def build(name, kw=None, keep=None):
 
 
 if __name__ == "__main__":
-    for name in CASES:
+    for name in list(CASES) + list(DIRECTED):
         if len(sys.argv) > 1 and name not in sys.argv[1:]:
             continue
         print(build(name), flush=True)
