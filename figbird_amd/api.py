@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
+from dataclasses import replace as dc_replace
 from typing import List, Optional
 
 import numpy as np
@@ -73,6 +74,27 @@ class FigGapQuality(C.Structure):
 QUAL_OFF, QUAL_ON = 0, 1
 
 
+class FigReadPlacement(C.Structure):
+    _fields_ = [("ll_drawn", c_double_p), ("ll_other", c_double_p), ("sum_other", c_double_p), ("off_other", c_i32_p), ("n_valid", c_i32_p),
+                ("pq", c_u8_p), ("state", c_u8_p)]
+
+
+# fig_read_placement::state / ::pq (include/figbird_hip.h)
+PLACE_OFF, PLACE_ON, PLACE_NONE, PLACE_MAX_PQ = 0, 1, 255, 60
+
+
+@dataclass
+class Placement:
+    """fig_read_placement of one call: the six per-read arrays are indexed like the unmapped part of draw_pos, state per gap"""
+    ll_drawn: np.ndarray
+    ll_other: np.ndarray
+    sum_other: np.ndarray
+    off_other: np.ndarray
+    n_valid: np.ndarray
+    pq: np.ndarray
+    state: np.ndarray
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -82,7 +104,7 @@ class FigStats(C.Structure):
 
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
            "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
-           "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality"]
+           "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality", "fig_batch_placement"]
 
 _lib = None
 _host = None
@@ -118,6 +140,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.fig_fill_resident_ex.argtypes = [C.c_void_p, C.POINTER(FigGapResults), C.POINTER(FigGapSupport)]
     if hasattr(lib, "fig_batch_quality"):             # (likewise)
         lib.fig_batch_quality.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigGapQuality)]
+    if hasattr(lib, "fig_batch_placement"):           # (likewise)
+        lib.fig_batch_placement.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigReadPlacement)]
     if path is None:
         _lib = lib
     return lib
@@ -146,6 +170,13 @@ def load_host_library() -> C.CDLL:
         _host.fighost_quality_phred.argtypes = [C.c_int64, c_double_p, C.c_char_p, c_u8_p]
         _host.fighost_quality_gaps_on.argtypes = [C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
         _host.fighost_run_write_quality.argtypes = [C.c_void_p, c_i32_p, c_i64_p, c_u8_p, c_u8_p, C.c_char_p, C.c_int]
+        _host.fighost_placement_li.argtypes = [C.POINTER(FigModel), c_double_p]
+        _host.fighost_placement_isz.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        _host.fighost_placement_isz.restype = C.c_int64
+        _host.fighost_placement_valid.argtypes = [C.POINTER(FigModel), C.c_int64]
+        _host.fighost_placement_phred.argtypes = [C.c_int64, c_double_p, c_double_p, c_double_p, c_u8_p]
+        _host.fighost_placement_gaps_on.argtypes = [C.c_int, C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
+        _host.fighost_run_write_placement.argtypes = [C.c_void_p, c_i32_p, c_u8_p, c_u8_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -290,6 +321,7 @@ class FillResult:
     draw: Optional[tuple] = None           # (draw_pos, draw_isz, draw_len) planes of fig_gap_results, when requested
     support: Optional[np.ndarray] = None   # int32 [total, 5]: read counts (A, C, G, T, other) behind raw[i], i.e. base x of gap g at str_off[g] + x
     support_origin: Optional[np.ndarray] = None   # int32 [n_gaps]: SUP_* mask (fig_gap_support::origin)
+    placement: Optional["Placement"] = None   # fig_read_placement of the fill's drawn unmapped reads, when requested
     quality: Optional[tuple] = None        # (loglik float64 [total, 4], phred uint8 [total], state uint8 [n_gaps]) of fig_gap_quality, indexed like raw
 
     @property
@@ -350,11 +382,67 @@ class Engine:
         self._check(self.lib.fig_fill_resident_ex(self.ctx, C.byref(r), C.byref(s)), "fig_fill_resident_ex")
         return sc, so
 
-    def quality(self, res: FillResult, origin: Optional[np.ndarray] = None):
+    def _n_ureads(self) -> int:
+        """unmapped reads of the resident batch as the library counts them: none under a model that is not unmapped-mode"""
+        if not self._cm.unmapped_flag or self.n_gaps <= 0 or not self._cb.u_read_off:
+            return 0
+        return int(self._cb.u_read_off[self.n_gaps])
+
+    def _filled_struct(self, what: str, res: FillResult):
+        """fig_gap_results of the strings and draw planes in `res` (and the arrays that keep it alive)"""
+        if res.draw is None:
+            raise ValueError(f"{what}: the fill result carries no draw planes (fill with draw=True)")
+        n = self.n_gaps
+        fl = np.ascontiguousarray(res.filled_len, dtype=np.int32); so = np.ascontiguousarray(res.str_off, dtype=np.int64)
+        if len(fl) < n or len(so) < n + 1:
+            raise ValueError(f"{what}: one length and one offset per gap of the resident batch")
+        fl = fl if n else np.zeros(1, dtype=np.int32)
+        raw = np.ascontiguousarray(res.raw, dtype=np.uint8) if res.raw is not None and len(res.raw) else np.zeros(1, dtype=np.uint8)
+        dpos, disz, dlen = (np.ascontiguousarray(a, dtype=np.int32) for a in res.draw)
+        dpos, disz, dlen = (a if len(a) else np.zeros(1, dtype=np.int32) for a in (dpos, disz, dlen))
+        r = FigGapResults()
+        r.filled_len = _p(fl, c_i32_p); r.str_off = _p(so, c_i64_p); r.str = C.cast(raw.ctypes.data, C.c_char_p); r.str_capacity = len(raw)
+        r.draw_pos = _p(dpos, c_i32_p); r.draw_isz = _p(disz, c_i32_p); r.draw_len = _p(dlen, c_i32_p)
+        return r, (fl, so, raw, dpos, disz, dlen)
+
+    def placement(self, res: FillResult, origin: Optional[np.ndarray] = None) -> "Placement":
+        """fig_batch_placement of the strings and draw planes in `res` against the resident batch; `origin` as for quality().
+        The buffers handed to the library start as 0xFF bytes, so that an element it failed to write shows."""
+        if not hasattr(self.lib, "fig_batch_placement"):
+            raise RuntimeError("placement needs fig_batch_placement, which this library does not export")
+        r, keep = self._filled_struct("placement", res)
+        n, nu = self.n_gaps, self._n_ureads()
+        if len(keep[3]) < nu:
+            raise ValueError("placement: one drawn offset per unmapped read of the resident batch")
+        org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+        if org is not None and len(org) < n:
+            raise ValueError("placement: one origin per gap of the resident batch")
+        m = max(nu, 1)
+        d = [np.zeros(m) for _ in range(3)]
+        for a in d:
+            a.view(np.uint8)[...] = 0xFF
+        off = np.full(m, -1, dtype=np.int32); nv = np.full(m, -1, dtype=np.int32)
+        pq = np.full(m, 0xFE, dtype=np.uint8); stt = np.full(max(n, 1), 0xFF, dtype=np.uint8)
+        rp = FigReadPlacement()
+        rp.ll_drawn = _p(d[0], c_double_p); rp.ll_other = _p(d[1], c_double_p); rp.sum_other = _p(d[2], c_double_p)
+        rp.off_other = _p(off, c_i32_p); rp.n_valid = _p(nv, c_i32_p); rp.pq = _p(pq, c_u8_p); rp.state = _p(stt, c_u8_p)
+        self._check(self.lib.fig_batch_placement(self.ctx, C.byref(r), None if org is None or not len(org) else _p(org, c_i32_p), C.byref(rp)), "fig_batch_placement")
+        return Placement(d[0][:nu], d[1][:nu], d[2][:nu], off[:nu], nv[:nu], pq[:nu], stt[:n])
+
+    def quality(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: Optional["Placement"] = None, min_pq: Optional[int] = None):
         """fig_batch_quality of the strings and draw planes in `res` against the resident batch; `origin` is
         FillResult.support_origin, or None for no origin test.  Returns (loglik [total, 4], phred [total], state [n_gaps]) with
         total = str_off[n_gaps]: base x of gap g at str_off[g] + x.  The buffers handed to the library start as 0xFF bytes, so
-        that an element it failed to write shows."""
+        that an element it failed to write shows.  placement=P, min_pq=k: the call sees a copy of the draw plane in which the
+        scored reads of P with pq < k are not drawn (INT32_MIN)."""
+        if (placement is None) != (min_pq is None):
+            raise ValueError("quality: placement and min_pq go together")
+        if placement is not None and res.draw is not None:
+            dpos = np.array(res.draw[0], dtype=np.int32)
+            pq = np.asarray(placement.pq)
+            drop = np.flatnonzero((pq != PLACE_NONE) & (pq < min_pq))
+            dpos[drop] = np.iinfo(np.int32).min
+            res = dc_replace(res, draw=(dpos, res.draw[1], res.draw[2]))
         if not hasattr(self.lib, "fig_batch_quality"):
             raise RuntimeError("quality needs fig_batch_quality, which this library does not export")
         if res.draw is None:
@@ -380,11 +468,15 @@ class Engine:
         self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), None if org is None or not len(org) else _p(org, c_i32_p), C.byref(gq)), "fig_batch_quality")
         return ll[:total], ph[:total], stt[:n]
 
-    def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False) -> FillResult:
-        """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins)."""
+    def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
+                      placement: bool = False) -> FillResult:
+        """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins);
+        placement=True likewise fills FillResult.placement (fig_batch_placement with the origins)."""
         if quality and not hasattr(self.lib, "fig_batch_quality"):
             raise RuntimeError("quality=True needs fig_batch_quality, which this library does not export")
-        draw = draw or quality; support = support or quality
+        if placement and not hasattr(self.lib, "fig_batch_placement"):
+            raise RuntimeError("placement=True needs fig_batch_placement, which this library does not export")
+        draw = draw or quality or placement; support = support or quality or placement
         n = self.n_gaps
         fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
         so = np.zeros(n + 1, dtype=np.int64); st = np.zeros(max(self.cap, 1), dtype=np.uint8)
@@ -427,6 +519,8 @@ class Engine:
             res.draw = (dpos[:nr], disz[:nr], dlen[:2 * n])
         if support:
             res.support = sup_c[:int(so[n])]; res.support_origin = sup_o[:n]
+        if placement:
+            res.placement = self.placement(res, res.support_origin)
         if quality:
             res.quality = self.quality(res, res.support_origin)
         return res
@@ -458,17 +552,21 @@ class Engine:
             self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
 
     def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False, quality: bool = False,
-                    keep_resident: bool = False) -> FillResult:
+                    keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
         resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
         read support as well (fields `support`, `support_origin`).  quality=True implies draw and support and runs
         fig_batch_quality before the batch is freed (field `quality`).  keep_resident=True leaves an uploaded batch resident
-        for a further call."""
+        for a further call.  placement=True likewise runs fig_batch_placement (field `placement`); with min_pq as well the
+        quality leaves out the scored reads below that pq (Engine.quality)."""
         if quality and not hasattr(self.lib, "fig_batch_quality"):
             raise RuntimeError("quality=True needs fig_batch_quality, which this library does not export")
-        draw = draw or quality; support = support or quality
-        qual = None
+        placement = placement or min_pq is not None
+        if placement and not hasattr(self.lib, "fig_batch_placement"):
+            raise RuntimeError("placement=True needs fig_batch_placement, which this library does not export")
+        draw = draw or quality or placement; support = support or quality or placement
+        qual = plc = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
@@ -490,9 +588,13 @@ class Engine:
         if n > 0 and resident:
             try:
                 sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
+                if placement:
+                    self.n_gaps = n; self._cb = cbatch
+                    plc = self.placement(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen)), sup_o)
                 if quality:
                     self.n_gaps = n
-                    qual = self.quality(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen)), sup_o)
+                    qual = self.quality(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen)), sup_o,
+                                        placement=plc if min_pq is not None else None, min_pq=min_pq)
             finally:
                 if not keep_resident:
                     self.lib.fig_batch_free(self.ctx)
@@ -505,12 +607,16 @@ class Engine:
             res.support_origin = sup_o[:n] if sup_o is not None else np.zeros(0, dtype=np.int32)
         if quality:
             res.quality = qual if qual is not None else (np.zeros((0, 4)), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
+        if placement:
+            z = np.zeros(0)
+            res.placement = plc if plc is not None else Placement(z, z, z, np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
         return res
 
-    def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False) -> FillResult:
+    def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
+             placement: bool = False) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement)
         finally:
             self.free_batch()
 

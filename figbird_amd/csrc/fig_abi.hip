@@ -22,6 +22,7 @@
 #include "fig_abi_host.h"
 #include "fig_quality.h"
 #include "fig_quality_host.h"
+#include "fig_placement.h"
 
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
@@ -707,6 +708,100 @@ extern "C" int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *f, const i
         for (int64_t i = f->str_off[g], e = f->str_off[g] + ncol[(size_t)g]; i < e; i++) q->phred[i] = fig_quality_phred(q->loglik + i * 4, f->str[i]);
     if (fig_knobs_from_env(ctx->dm.unmapped).log)
         fprintf(stderr, "[figqual] gaps on %zu of %lld, columns %lld, reads %lld, kernel %.3f ms\n", list.size(), (long long)ng, (long long)cols, (long long)reads, ms);
+    return FIG_OK;
+}
+
+// Placement confidence per drawn unmapped read (fig_placement.h: the kernel; fig_placement_host.h: li, insert size, validity, which
+// gaps are on, Phred).  Beside the fill like fig_batch_quality: per-call device buffers, the library's stream, nothing of the
+// resident batch or the model is written.
+extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_read_placement *p) {
+    if (!ctx || !f || !p || !ctx->have_batch || !ctx->have_model) return FIG_EINVAL;
+    if (!f->filled_len || !f->str_off || !f->draw_pos || !f->draw_len) return FIG_EINVAL;
+    if (!p->ll_drawn || !p->ll_other || !p->sum_other || !p->off_other || !p->n_valid || !p->pq || !p->state) return FIG_EINVAL;
+    hipSetDevice(ctx->device);
+    const int64_t ng = ctx->n_gaps, nu = ctx->n_ureads;
+    if (f->str_off[0] < 0) return FIG_EINVAL;
+    for (int64_t g = 0; g < ng; g++) if (f->str_off[g + 1] < f->str_off[g]) return FIG_EINVAL;
+    const int64_t total = f->str_off[ng];
+    if (total > 0 && !f->str) return FIG_EINVAL;
+    const FigDevBatch &db = ctx->db;
+    const int L = ctx->dm.L, MI = ctx->dm.max_insert;
+    std::vector<FigDevGap> hg((size_t)ng);
+    std::vector<double> he((size_t)L), home((size_t)L), tabs((size_t)fig_quality_tab_doubles(L)), insd((size_t)MI), li((size_t)MI);
+    if (ng > 0) FIG_HIP(hipMemcpyAsync(hg.data(), db.gaps, (size_t)ng * sizeof(FigDevGap), hipMemcpyDeviceToHost, ctx->stream));
+    FIG_HIP(hipMemcpyAsync(he.data(), ctx->dm.e, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FIG_HIP(hipMemcpyAsync(home.data(), ctx->dm.ome1, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FIG_HIP(hipMemcpyAsync(insd.data(), ctx->dm.insd, (size_t)MI * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    FIG_HIP(hipStreamSynchronize(ctx->stream));
+    fig_quality_tables(L, he.data(), home.data(), ctx->dm.T, tabs.data(), tabs.data() + L, tabs.data() + 2 * L);
+    fig_placement_li(MI, insd.data(), li.data());
+    // which gaps are on, their work items, and the bounds of what the kernel will index with
+    std::vector<int32_t> items;
+    std::vector<int32_t> ncol((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<uint8_t> scored((size_t)std::max<int64_t>(nu, 1), 0);
+    int64_t gaps_on = 0, reads = 0, placements = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        const int32_t n = f->filled_len[g];
+        p->state[g] = fig_placement_gap_on(ctx->dm.unmapped != 0, n, f->draw_len[2 * g], f->draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+        if (p->state[g] != FIG_PLACE_ON) continue;
+        if (n > (1 << 30) || f->str_off[g] + n > f->str_off[g + 1]) return FIG_EINVAL;
+        const int64_t base = hg[(size_t)g].uBase, cnt = hg[(size_t)g].nU;
+        if (base < 0 || cnt < 0 || base + cnt > nu) return FIG_EINVAL;
+        const int64_t drawn = fig_placement_check_offsets(f->draw_pos + base, cnt);
+        if (drawn < 0) return FIG_EINVAL;
+        gaps_on++; ncol[(size_t)g] = n; reads += drawn;
+        for (int64_t r = 0; r < cnt; r++) scored[(size_t)(base + r)] = f->draw_pos[base + r] != INT32_MIN;
+        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_P_CHUNK) {               // a chunk without a drawn read is no work item
+            bool any = false;
+            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_P_CHUNK, cnt); r++) any = any || scored[(size_t)(base + r)];
+            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
+        }
+    }
+    for (int64_t r = 0; r < nu; r++) {
+        p->ll_drawn[r] = 0.0; p->ll_other[r] = 0.0; p->sum_other[r] = 0.0; p->off_other[r] = INT32_MIN; p->n_valid[r] = 0; p->pq[r] = FIG_PLACE_NONE;
+    }
+    float ms = 0;
+    if (!items.empty()) {
+        FigTmpBufs tmp;
+        auto up = [&](const void *src, size_t bytes) -> void * {
+            void *q = tmp.alloc(bytes);
+            if (q && bytes && hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
+            return q;
+        };
+        FigPlaceArgs A;
+        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_pos = db.u.pos; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank;
+        A.L = L; A.Tmin = ctx->dm.Tmin; A.Tmax = ctx->dm.Tmax; A.max_insert = MI;
+        A.draw_pos = (const int32_t *)up(f->draw_pos, (size_t)nu * 4);
+        A.items = (const int32_t *)up(items.data(), items.size() * 4);
+        A.ncol = (const int32_t *)up(ncol.data(), (size_t)ng * 4);
+        A.str_off = (const int64_t *)up(f->str_off, (size_t)(ng + 1) * 8);
+        A.str = (const char *)up(f->str, (size_t)total);
+        A.tabs = (const double *)up(tabs.data(), tabs.size() * sizeof(double));
+        A.li = (const double *)up(li.data(), li.size() * sizeof(double));
+        double *dd = (double *)tmp.alloc((size_t)nu * 3 * sizeof(double));
+        int32_t *di = (int32_t *)tmp.alloc((size_t)nu * 2 * sizeof(int32_t));
+        if (!A.draw_pos || !A.items || !A.ncol || !A.str_off || !A.str || !A.tabs || !A.li || !dd || !di) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
+        A.ll_drawn = dd; A.ll_other = dd + nu; A.sum_other = dd + 2 * nu; A.off_other = di; A.n_valid = di + nu;
+        std::vector<double> hd((size_t)nu * 3);
+        std::vector<int32_t> hi((size_t)nu * 2);
+        FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        hipLaunchKernelGGL(fig_placement_kernel, dim3((unsigned)(items.size() / 2)), dim3(FIG_P_NT), 0, ctx->stream, A);
+        FIG_HIP(hipGetLastError());
+        FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        FIG_HIP(hipMemcpyAsync(hd.data(), dd, hd.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        FIG_HIP(hipMemcpyAsync(hi.data(), di, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        FIG_HIP(hipStreamSynchronize(ctx->stream));
+        FIG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        for (int64_t r = 0; r < nu; r++) {
+            if (!scored[(size_t)r]) continue;
+            p->ll_drawn[r] = hd[(size_t)r]; p->ll_other[r] = hd[(size_t)(nu + r)]; p->sum_other[r] = hd[(size_t)(2 * nu + r)];
+            p->off_other[r] = hi[(size_t)r]; p->n_valid[r] = hi[(size_t)(nu + r)];
+            p->pq[r] = fig_placement_phred(p->ll_drawn[r], p->ll_other[r], p->sum_other[r]);
+            placements += p->n_valid[r];
+        }
+    }
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figplace] gaps on %lld of %lld, reads scored %lld, placements scored %lld, kernel %.3f ms\n", (long long)gaps_on, (long long)ng, (long long)reads, (long long)placements, ms);
     return FIG_OK;
 }
 

@@ -3,6 +3,7 @@
 #include "fig_host.h"
 #include "../fig_gaprules.h"
 #include "../fig_quality_host.h"
+#include "../fig_placement_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -764,6 +765,20 @@ bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::stri
     return true;
 }
 
+bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+    FILE *f = fopen((a.tmp + "gapplacement.txt").c_str(), "w");
+    if (!f) { err = "can't write gapplacement.txt"; return false; }
+    std::string Q;
+    for (size_t g = 0; g < b.gap_contig.size(); g++) {
+        const int64_t r0 = g < b.u_read_off.size() ? b.u_read_off[g] : 0, r1 = g + 1 < b.u_read_off.size() ? b.u_read_off[g + 1] : r0;
+        Q.clear();
+        for (int64_t k = r0; k < r1; k++) { const uint8_t pq = r.place_pq[(size_t)k]; Q += pq == FIG_PLACE_NONE ? '~' : (char)(33 + pq); }
+        fprintf(f, "%d\t%d\t%ld\t%d\t%d\t%d\t%ld\t%s\n", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g], r.filled_len[g], (int)r.place_state[g], (long)(r1 - r0), Q.c_str());
+    }
+    fclose(f);
+    return true;
+}
+
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     FILE *f = fopen((a.tmp + "draw.txt").c_str(), "w");
     if (!f) { err = "can't write draw.txt"; return false; }
@@ -1095,5 +1110,42 @@ extern "C" int fighost_run_write_quality(void *h, const int32_t *filled_len, con
     R.qual_state.assign(state, state + ng);
     std::string e;
     if (!fighost::write_quality(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
+    return 0;
+}
+
+// ------------------------------------------------------------------ placement confidence (fig_placement_host.h)
+// li[max_insert_size] of the model, as fig_batch_placement builds it
+extern "C" int fighost_placement_li(const fig_model *m, double *li) {
+    if (!m || !m->insert_len_dist_smoothed || !li || m->max_insert_size <= 0) return -1;
+    fig_placement_li(m->max_insert_size, m->insert_len_dist_smoothed, li);
+    return 0;
+}
+
+// insert size of one placement, and 1 iff it is valid under the model's thresholds and table
+extern "C" int64_t fighost_placement_isz(int64_t pos, int64_t gap_start, int32_t G0, int32_t n, int32_t len, int32_t o) { return fig_placement_isz(pos, gap_start, G0, n, len, o); }
+extern "C" int fighost_placement_valid(const fig_model *m, int64_t isz) { return fig_placement_valid(isz, m->insert_threshold_min, m->insert_threshold_max, m->max_insert_size) ? 1 : 0; }
+
+// pq of `n` scored reads from their three doubles
+extern "C" int fighost_placement_phred(int64_t n, const double *ll_drawn, const double *ll_other, const double *sum_other, uint8_t *pq) {
+    for (int64_t i = 0; i < n; i++) pq[i] = fig_placement_phred(ll_drawn[i], ll_other[i], sum_other[i]);
+    return 0;
+}
+
+// FIG_PLACE_* of `ng` gaps from the mode, their string lengths, draw headers [ng*2] and origins (NULL = no origin test) -> state [ng]
+extern "C" int fighost_placement_gaps_on(int unmapped_model, int64_t ng, const int32_t *filled_len, const int32_t *draw_len, const int32_t *origin, uint8_t *state) {
+    for (int64_t g = 0; g < ng; g++) state[g] = fig_placement_gap_on(unmapped_model != 0, filled_len[g], draw_len[2 * g], draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+    return 0;
+}
+
+// gapplacement.txt of the WHOLE gap set (FIGFILL_PLACEMENT=1): pq [unmapped reads] indexed like draw_pos, state [n_gaps]
+extern "C" int fighost_run_write_placement(void *h, const int32_t *filled_len, const uint8_t *pq, const uint8_t *state, char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size(), nu = r->B.u_anchor_pos.size();
+    fighost::Results R;
+    R.filled_len.assign(filled_len, filled_len + ng);
+    R.place_pq.assign(pq, pq + nu);
+    R.place_state.assign(state, state + ng);
+    std::string e;
+    if (!fighost::write_placement(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
     return 0;
 }

@@ -90,6 +90,8 @@ struct Results {
     std::vector<int32_t> sup_counts, sup_origin;
     // per-base quality (fig_gap_quality), when asked for: Phred [str.size()] indexed like str, and FIG_QUAL_* [n_gaps]
     std::vector<uint8_t> qual_phred, qual_state;
+    // placement confidence (fig_read_placement), when asked for: pq [unmapped reads] indexed like draw_pos, and FIG_PLACE_* [n_gaps]
+    std::vector<uint8_t> place_pq, place_state;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
@@ -101,6 +103,10 @@ bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::stri
 // gapquality.txt (no counterpart in the reference): per gap `g contig start G0 n state Q`, tab-separated, the first five fields
 // as in gapout.txt, state = FIG_QUAL_*, Q = n characters of Phred+33 (empty for n <= 0)
 bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gapplacement.txt (no counterpart in the reference): per gap `g contig start G0 n state R Q`, tab-separated, the first five fields
+// as in gapout.txt, state = FIG_PLACE_*, R = the gap's unmapped read count, Q = R characters: Phred+33 of the read's pq, or '~'
+// for a read that was not scored
+bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // filledContigs.fa + Ncount.txt (FillGaps.cpp:708-926)
 bool write_scaffold(const RunArgs &a, const Scaffold &sc, const Batch &b, const Results &r, std::string &err);
 

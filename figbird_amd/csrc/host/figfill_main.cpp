@@ -32,12 +32,43 @@ static bool want_support() { const char *s = getenv("FIGFILL_SUPPORT"); return s
 // FIGFILL_QUALITY=1: the fill with the support call (for the origins), then fig_batch_quality, and <tmp>/gapquality.txt
 static bool want_quality() { const char *s = getenv("FIGFILL_QUALITY"); return s && atoi(s) == 1; }
 
-// the per-base quality of the fill `fr` just returned (the batch still resident): R.qual_phred / R.qual_state
-static int quality_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng) {
+// fig_batch_placement likewise: FIGFILL_PLACEMENT=1 or FIGFILL_QUALITY_MINPQ on a library without it is an error before anything
+// is filled or written.
+extern "C" int fig_batch_placement(fig_ctx *, const fig_gap_results *, const int32_t *, fig_read_placement *) __attribute__((weak));
+
+// FIGFILL_PLACEMENT=1: the fill with the support call (for the origins), then fig_batch_placement, and <tmp>/gapplacement.txt
+static bool want_placement_file() { const char *s = getenv("FIGFILL_PLACEMENT"); return s && atoi(s) == 1; }
+
+// FIGFILL_QUALITY_MINPQ=<k> (only together with FIGFILL_QUALITY=1): the quality leaves out scored reads with pq < k; -1 = not set
+static int quality_min_pq() { const char *s = getenv("FIGFILL_QUALITY_MINPQ"); return s && *s && want_quality() ? atoi(s) : -1; }
+
+// the placement call is needed for the file and for the filter
+static bool want_placement() { return want_placement_file() || quality_min_pq() >= 0; }
+
+// the placement confidence of the fill `fr` just returned (the batch still resident): R.place_pq / R.place_state
+static int placement_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu) {
+    const size_t m = (size_t)std::max<int64_t>(nu, 1);
+    R.place_pq.assign(m, FIG_PLACE_NONE); R.place_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<double> d(m * 3, 0.0);
+    std::vector<int32_t> i(m * 2, 0);
+    fig_read_placement rp;
+    rp.ll_drawn = d.data(); rp.ll_other = d.data() + m; rp.sum_other = d.data() + 2 * m; rp.off_other = i.data(); rp.n_valid = i.data() + m;
+    rp.pq = R.place_pq.data(); rp.state = R.place_state.data();
+    return fig_batch_placement(ctx, fr, R.sup_origin.data(), &rp);
+}
+
+// the per-base quality of the fill `fr` just returned (the batch still resident): R.qual_phred / R.qual_state.  With
+// FIGFILL_QUALITY_MINPQ the call sees a copy of the draw plane in which the scored reads below the bound are not drawn.
+static int quality_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu) {
     R.qual_phred.assign((size_t)std::max<int64_t>(fr->str_capacity, 1), 0); R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
     std::vector<double> ll((size_t)std::max<int64_t>(fr->str_off[ng], 1) * 4, 0.0);
     fig_gap_quality gq; gq.loglik = ll.data(); gq.phred = R.qual_phred.data(); gq.state = R.qual_state.data();
-    return fig_batch_quality(ctx, fr, R.sup_origin.data(), &gq);
+    const int k = quality_min_pq();
+    if (k < 0) return fig_batch_quality(ctx, fr, R.sup_origin.data(), &gq);
+    std::vector<int32_t> kept(R.draw_pos);
+    for (int64_t r = 0; r < nu; r++) if (R.place_pq[(size_t)r] != FIG_PLACE_NONE && R.place_pq[(size_t)r] < k) kept[(size_t)r] = INT32_MIN;
+    fig_gap_results f2 = *fr; f2.draw_pos = kept.data();
+    return fig_batch_quality(ctx, &f2, R.sup_origin.data(), &gq);
 }
 
 // the fill, with R.sup_counts / R.sup_origin sized and filled when `support`
@@ -93,10 +124,12 @@ static void shard_fill(int device, const fig_model *fm, const Scaffold *sc, Shar
     fr.filled_len = R.filled_len.data(); fr.gaptofill = R.gaptofill.data(); fr.str_off = R.str_off.data();
     fr.str = &R.str[0]; fr.str_capacity = (int64_t)R.str.size();
     fr.draw_pos = R.draw_pos.data(); fr.draw_isz = R.draw_isz.data(); fr.draw_len = R.draw_len.data();
-    rc = fill_resident(S->ctx, &fr, R, ng, want_support() || want_quality());
+    rc = fill_resident(S->ctx, &fr, R, ng, want_support() || want_quality() || want_placement());
     fig_get_stats(S->ctx, &S->st);
     if (rc) return shard_fail(S, rc, std::string("fig_fill_resident on device ") + std::to_string(device));
-    if (want_quality() && (rc = quality_resident(S->ctx, &fr, R, ng))) return shard_fail(S, rc, std::string("fig_batch_quality on device ") + std::to_string(device));
+    const int64_t snu = (int64_t)S->sub.u_anchor_pos.size();
+    if (want_placement() && (rc = placement_resident(S->ctx, &fr, R, ng, snu))) return shard_fail(S, rc, std::string("fig_batch_placement on device ") + std::to_string(device));
+    if (want_quality() && (rc = quality_resident(S->ctx, &fr, R, ng, snu))) return shard_fail(S, rc, std::string("fig_batch_quality on device ") + std::to_string(device));
     fig_ctx_destroy(S->ctx); S->ctx = nullptr;
 }
 
@@ -138,8 +171,9 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         st.n_launches += runs[r].st.n_launches;
     }
     R.str.clear();
-    const bool support = want_support() || want_quality(), quality = want_quality();
+    const bool support = want_support() || want_quality() || want_placement(), quality = want_quality(), placement = want_placement();
     if (support) R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    if (placement) { R.place_pq.assign((size_t)std::max<int64_t>(NU, 1), FIG_PLACE_NONE); R.place_state.assign((size_t)std::max<int64_t>(ng, 1), 0); }
     if (quality) R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
     for (int64_t g = 0; g < ng; g++) {
         const ShardRun &S = runs[owner[g]]; const int64_t k = local[g];
@@ -158,7 +192,11 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         const int64_t nu = B.u_read_off[g + 1] - B.u_read_off[g], np = B.p_read_off[g + 1] - B.p_read_off[g];
         const int64_t snu = (int64_t)S.sub.u_anchor_pos.size();
         for (int64_t i = 0; i < nu; i++) { R.draw_pos[B.u_read_off[g] + i] = S.R.draw_pos[S.sub.u_read_off[k] + i]; R.draw_isz[B.u_read_off[g] + i] = S.R.draw_isz[S.sub.u_read_off[k] + i]; }
-        for (int64_t i = 0; i < np; i++) { R.draw_pos[NU + B.p_read_off[g] + i] = S.R.draw_pos[snu + S.sub.p_read_off[k] + i]; R.draw_isz[NU + B.p_read_off[g] + i] = S.R.draw_isz[snu + S.sub.p_read_off[k] + i]; }
+        if (placement) {                                  // one pq per unmapped read, in the order of the draw plane
+            for (int64_t i = 0; i < nu; i++) R.place_pq[B.u_read_off[g] + i] = S.R.place_pq[S.sub.u_read_off[k] + i];
+            R.place_state[g] = S.R.place_state[k];
+        }
+        for (int64_t i = 0; i < np; i++) { R.draw_pos[NU +B.p_read_off[g] + i] = S.R.draw_pos[snu + S.sub.p_read_off[k] + i]; R.draw_isz[NU + B.p_read_off[g] + i] = S.R.draw_isz[snu + S.sub.p_read_off[k] + i]; }
     }
     R.str_off[ng] = (int64_t)R.str.size();
     if (R.str.empty()) R.str.assign(1, 'N');
@@ -194,6 +232,8 @@ int main(int argc, char **argv) {
         }
         if (devices.empty()) return fail("figfill: FIGFILL_DEVICES must be a comma-separated list of GPU ordinals");
     }
+    if (want_placement() && !fig_batch_placement)
+        return fail("figfill: FIGFILL_PLACEMENT=1 and FIGFILL_QUALITY_MINPQ need fig_batch_placement, which the library behind this build does not export");
     if (want_quality() && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
     setenv("GPU_MAX_HW_QUEUES", "8", 0);                 // one hardware queue per scheduler lane; before any thread or HIP call (fig_abi.hip: fig_ctx_create)
     auto t0 = std::chrono::steady_clock::now();
@@ -238,6 +278,7 @@ int main(int argc, char **argv) {
         if (!write_scaffold(a, sc, B, R, err)) return fail(err);
         if (want_support() && !write_support(a, B, R, err)) return fail(err);
         if (want_quality() && !write_quality(a, B, R, err)) return fail(err);
+        if (want_placement_file() && !write_placement(a, B, R, err)) return fail(err);
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         printf("Time taken = %g seconds (%zu GPUs; slowest shard's device kernels %.3f ms, %lld placeReads calls)\n", secs, devices.size(), st.kernel_ms, (long long)st.place_calls);
         printf("======================================\n");
@@ -278,12 +319,14 @@ int main(int argc, char **argv) {
         rc = fig_batch_probe_reach(ctx, reach.data());
         if (!rc) { ot_presets_from_reach(B, reach.data()); rc = fig_batch_set_ot_preset(ctx, B.gap_ot_preset.data()); }
     }
-    if (!rc) rc = fill_resident(ctx, &fr, R, ng, want_support() || want_quality());
+    if (!rc) rc = fill_resident(ctx, &fr, R, ng, want_support() || want_quality() || want_placement());
     fig_stats st; memset(&st, 0, sizeof(st)); fig_get_stats(ctx, &st);
-    int qrc = 0;
-    if (!rc && want_quality()) qrc = quality_resident(ctx, &fr, R, ng);
+    int qrc = 0, prc = 0;
+    if (!rc && want_placement()) prc = placement_resident(ctx, &fr, R, ng, (int64_t)B.u_anchor_pos.size());
+    if (!rc && !prc && want_quality()) qrc = quality_resident(ctx, &fr, R, ng, (int64_t)B.u_anchor_pos.size());
     fig_ctx_destroy(ctx);
     if (rc) return fail(std::string("figfill: fill: ") + fig_strerror(rc));
+    if (prc) return fail(std::string("figfill: fig_batch_placement: ") + fig_strerror(prc));
     if (qrc) return fail(std::string("figfill: fig_batch_quality: ") + fig_strerror(qrc));
 
     if (!write_gapout(a, B, R, err)) return fail(err);
@@ -292,6 +335,7 @@ int main(int argc, char **argv) {
     if (!write_scaffold(a, sc, B, R, err)) return fail(err);
     if (want_support() && !write_support(a, B, R, err)) return fail(err);
     if (want_quality() && !write_quality(a, B, R, err)) return fail(err);
+    if (want_placement_file() && !write_placement(a, B, R, err)) return fail(err);
     if (trace) {
         FILE *f = fopen(trace, "w");
         if (f) {

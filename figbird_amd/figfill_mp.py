@@ -39,6 +39,14 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     # FIGFILL_QUALITY=1: also gapquality.txt, the per-base Phred (fig_gap_quality); the fill then runs with the support call
     m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_QUALITY", ""))
     quality = m is not None and int(m.group(0)) == 1
+    # FIGFILL_PLACEMENT=1: also gapplacement.txt, the placement confidence per drawn unmapped read (fig_read_placement);
+    # FIGFILL_QUALITY_MINPQ=<k> (only with FIGFILL_QUALITY=1): the quality leaves out the scored reads with pq < k
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_PLACEMENT", ""))
+    placement = m is not None and int(m.group(0)) == 1
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_QUALITY_MINPQ", ""))
+    min_pq = int(m.group(0)) if (m is not None and quality) else None
+    if min_pq is not None and min_pq < 0:
+        min_pq = None
     own_pg = False
     if world > 1 and not dist.is_initialized():
         be = backend or ("nccl" if torch.cuda.is_available() else "gloo")
@@ -102,7 +110,7 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
             preset = np.zeros(max(n, 1), dtype=np.uint8)
             host.fighost_run_ot_presets(h, api._p(reach, api.c_u8_p), api._p(preset, api.c_u8_p))
             eng.set_ot_preset(preset[mine] if len(mine) else np.zeros(0, dtype=np.uint8))
-            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality, quality=quality)
+            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement, quality=quality, placement=placement, min_pq=min_pq)
             st = eng.stats()
             eng.close()
         except Exception as e:
@@ -122,7 +130,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
         sup_x = [res.support.reshape(-1), res.support_origin] if support else []
         # and so does the quality: the shard's Phred, one per string byte in shard order, and its states (widened to the extras' int32)
         qual_x = [res.quality[1].astype(np.int32), res.quality[2].astype(np.int32)] if quality else []
-        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz] + sup_x + qual_x)
+        # and the placement: the shard's pq, one per unmapped read in shard order, and its states
+        place_x = [res.placement.pq.astype(np.int32), res.placement.state.astype(np.int32)] if placement else []
+        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz] + sup_x + qual_x + place_x)
         wrc = 0
         try:
             fl, gt, ps, per_rank = out
@@ -134,11 +144,13 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 g_len = np.full(max(2 * n, 1), -1, dtype=np.int32)
                 g_sup = np.zeros((max(int(ps.off[-1]), 1), 5), dtype=np.int32); g_org = np.zeros(max(n, 1), dtype=np.int32)
                 g_phr = np.zeros(max(int(ps.off[-1]), 1), dtype=np.uint8); g_qst = np.zeros(max(n, 1), dtype=np.uint8)
+                g_ppq = np.full(max(NU, 1), api.PLACE_NONE, dtype=np.uint8); g_pst = np.zeros(max(n, 1), dtype=np.uint8)
                 for ids, r_len, r_pos, r_isz, *r_x in per_rank:
                     ids = np.asarray(ids, dtype=np.int64)
                     if len(ids) == 0:
                         continue
-                    r_sup, r_qual = (r_x[:2], r_x[2:]) if support else ([], r_x)
+                    r_sup, r_x = (r_x[:2], r_x[2:]) if support else ([], r_x)
+                    r_qual, r_place = (r_x[:2], r_x[2:]) if quality else ([], r_x)
                     if support or quality:      # a shard's strings lie back to back in its own gap order; ps.off is the global layout
                         ln = np.maximum(fl[ids], 0).astype(np.int64)
                         src0 = np.cumsum(ln) - ln
@@ -155,6 +167,10 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                     src_u = np.arange(su_, dtype=np.int64)
                     dst_u = np.repeat(uo[ids] - (np.cumsum(cu) - cu), cu) + src_u
                     g_pos[dst_u] = r_pos[:su_]; g_isz[dst_u] = r_isz[:su_]
+                    if placement and unmapped:
+                        g_ppq[dst_u] = r_place[0][:su_]
+                    if placement:
+                        g_pst[ids] = r_place[1]
                     sp_ = int(cp.sum())
                     src_p = np.arange(sp_, dtype=np.int64)
                     dst_p = NU + np.repeat(po[ids] - (np.cumsum(cp) - cp), cp) + src_p
@@ -169,6 +185,8 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 if wrc == 0 and quality:
                     wrc = host.fighost_run_write_quality(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
                                                          api._p(g_phr, api.c_u8_p), api._p(g_qst, api.c_u8_p), err, 512)
+                if wrc == 0 and placement:
+                    wrc = host.fighost_run_write_placement(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(g_ppq, api.c_u8_p), api._p(g_pst, api.c_u8_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

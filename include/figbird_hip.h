@@ -183,6 +183,60 @@ typedef struct fig_gap_quality {
     uint8_t *state;    /* [n_gaps] FIG_QUAL_* */
 } fig_gap_quality;
 
+/* Optional placement confidence per drawn unmapped read (fig_batch_placement): could the read have gone elsewhere?  The support and
+ * quality planes take the final placement of every read as a fact; in a repeat a read fits several offsets equally well and the
+ * MLE pass keeps the first maximum.  This call scores EVERY placement of every drawn read against the emitted sequence, one
+ * E-step's worth of work per gap, and reports the drawn placement next to the best other one (what aligners call MAPQ).
+ *
+ * Sequence of gap g.  n = filled_len[g].  For an integer column x, S(x) is the emitted byte str[str_off[g] + x] for 0 <= x < n,
+ * the contig base at gap_start + x for x < 0, the contig base at gap_start + G0 + (x - n) for x >= n; a position outside the
+ * contig, or a byte outside ACGT, is N.  (On the device: the 2 x 208 flank codes of the resident batch.)  No column beyond
+ * +-(200 - 1) of the string is ever needed.
+ *
+ * Placements of unmapped read r (length len, anchor pos = u_anchor_pos[r], reverse bit rev): the offsets o in [-(len-1), n-1],
+ * base j on column o + j.  Insert size of a placement: pos < gap_start (left anchor): isz(o) = gap_start - pos + len + o;
+ * otherwise (right anchor): isz(o) = pos + (n - G0) - gap_start + len - o  (the reference's tempInsertSize, Figbird.cpp finalize).
+ * A placement is VALID iff insert_threshold_min <= isz <= insert_threshold_max and 0 <= isz < max_insert_size.
+ *
+ * Score.  lm, le, lt are fig_gap_quality's tables; li[s] = log10(insertLengthDistSmoothed[s]) (the C library's log10, log10(0) =
+ * -inf is kept); lq = -0x1.34413509f79ffp-1 (log10 of 1/4).  Lr(o) = li[isz(o)], then for j = 0 .. len-1 in ascending order
+ * Lr = Lr + t_j, each + one IEEE double addition; a read base outside ACGT is skipped; with c = S(o + j), s the read base and
+ * k = len-1-j if rev else j:  t_j = lq if c is N;  lm[k] if c == s;  otherwise le[k] + lt[c][s].  Only -inf can meet -inf, so no
+ * NaN arises.  The device only adds table entries in that order.
+ *
+ * A gap is FIG_PLACE_ON iff the model is unmapped-mode, draw_len[2g] >= 0 and draw_len[2g+1] < 0, and fig_gap_quality's rule
+ * holds (n > 0, the header equals n, origins given: FINAL without ORIGINAL).  Partial reads are anchored by their clip and are not
+ * scored.  A read is SCORED iff its gap is on and draw_pos[r] != INT32_MIN.
+ *
+ * Per scored read, o* = draw_pos[r] (arrays indexed like the unmapped part of draw_pos):
+ *   ll_drawn   Lr(o*), or -inf if o* is not a valid placement
+ *   ll_other   the greatest Lr(o) over valid o != o*; -inf if there is none
+ *   off_other  the smallest o that attains ll_other; INT32_MIN if there is no valid o != o*
+ *   n_valid    the number of valid placements, o* included if it is valid
+ *   sum_other  with M = max(ll_drawn, ll_other): 0.0 if M is -inf, otherwise the sum of 10^(Lr(o) - M) over valid o != o* with
+ *              Lr(o) > -inf (a sum of positive terms: the device adds them in an order of its own, with its own exp10)
+ *   pq         on the host: 0 if ll_drawn is -inf; otherwise w = pow(10, ll_drawn - M), perr = sum_other / (sum_other + w);
+ *              60 if perr == 0, else floor(-10*log10(perr) + 0.5) clamped to 0..60
+ * The first four are exact by construction.  An unscored read gets ll_drawn = ll_other = sum_other = 0.0, off_other INT32_MIN,
+ * n_valid 0 and pq 255 (FIG_PLACE_NONE), written by the library whatever the buffers held.
+ *
+ * Limits of the number: a uniform prior over the bases of an N column; substitutions only; the other reads' placements do not
+ * enter; and the sequence is the EMITTED one, not the one the MLE pass placed against -- after recheck_sequence masks columns a
+ * read may now prefer another offset, which is reported (ll_other > ll_drawn, pq 0), not hidden. */
+#define FIG_PLACE_OFF 0
+#define FIG_PLACE_ON  1
+#define FIG_PLACE_NONE 255   /* pq of a read that was not scored */
+#define FIG_PLACE_MAX_PQ 60
+typedef struct fig_read_placement {
+    double  *ll_drawn;   /* [n_ureads] */
+    double  *ll_other;   /* [n_ureads] */
+    double  *sum_other;  /* [n_ureads] */
+    int32_t *off_other;  /* [n_ureads] */
+    int32_t *n_valid;    /* [n_ureads] */
+    uint8_t *pq;         /* [n_ureads] */
+    uint8_t *state;      /* [n_gaps] FIG_PLACE_* */
+} fig_read_placement;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -235,6 +289,13 @@ int fig_batch_set_ot_preset(fig_ctx *ctx, const uint8_t *preset);
  * with str_off not leaving filled_len[g] bytes to gap g, or with a drawn offset |o| >= 2^20 in a gap that is on.  With
  * FIG_SCHED_LOG set, one "[figqual]" line on stderr: gaps on, columns, reads, HIP-event milliseconds of the kernel. */
 int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, fig_gap_quality *q);
+
+/* Placement confidence of the drawn unmapped reads of `filled` against the RESIDENT batch (see fig_read_placement); `filled` and
+ * origin as for fig_batch_quality (draw_isz is not read).  Reads the resident batch and the model and writes neither.  FIG_EINVAL
+ * without a resident batch, with a needed pointer NULL, with str_off not leaving filled_len[g] bytes to gap g, or with a drawn
+ * offset |o| >= 2^20 in a gap that is on.  With FIG_SCHED_LOG set, one "[figplace]" line on stderr: gaps on, reads scored,
+ * placements scored, HIP-event milliseconds of the kernel. */
+int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, fig_read_placement *p);
 
 int fig_get_stats(const fig_ctx *ctx, fig_stats *out);
 
