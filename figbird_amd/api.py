@@ -98,7 +98,7 @@ class Placement:
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
-                ("n_launches", C.c_int32), ("pad0", C.c_int32), ("spec_flops", C.c_double),
+                ("n_launches", C.c_int32), ("cont_chunks", C.c_int32), ("spec_flops", C.c_double),
                 ("mle_alg_flops", C.c_double), ("mle_exec_flops", C.c_double)]
 
 

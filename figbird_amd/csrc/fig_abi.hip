@@ -113,14 +113,118 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_probe_kernel(FigD
     fig_pop_loop(E, B, A, [&] { return fig_src_order(B, A); }, [&](int gi) { fig_item_probe<LDS_TAB>(E, work, gi); });
 }
 
+// ---- the continuous form of the eval launch (fig_engine_sched.h: fig_item_continue): hand-over between workgroups.
+// Workgroups of one gap sit on different XCDs, whose L2s are not coherent with each other: everything one workgroup leaves for
+// another (a candidate's slot, the replayed state, a continuation) is followed by a device-scope fence of every lane that wrote,
+// then one device-scope atomic of lane 0; the reader does the atomic first and the fence after it.  No workgroup ever waits for
+// another: nothing below spins, and every loop's trip count is fixed when it is entered.
+FIG_D int fig_ld_acquire(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT); }
+FIG_D int fig_ld_relaxed(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// One more item of the gap's chunk of n is done.  True, in every lane, in the one workgroup that finished the chunk; it leaves
+// the gap's count at zero for the next chunk, which nobody starts before this workgroup (or the host) has published it.
+FIG_D bool fig_chunk_finished(FigEng &E, const FigDevBatch &B, int gi, int n) {
+    __threadfence();
+    __syncthreads();
+    if (E.tid == 0) {
+        const int done = __hip_atomic_fetch_add(B.gap_pending + gi, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1;
+        if (done == n) __hip_atomic_store(B.gap_pending + gi, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        E.S->bc_i = done == n;
+    }
+    __syncthreads();
+    const bool last = E.S->bc_i != 0;
+    __syncthreads();
+    if (last) __threadfence();
+    return last;
+}
+
+// Publish `c` if the lane's array has room -- and, for a chunk, if enough workgroups of the launch are still there to take
+// it: a workgroup that found nothing to claim has left for good, and a chunk published to an emptying launch would run
+// item after item in the few that remain.  Otherwise the gap stays as the replay left it (FIG_GAP_MORE / FIG_GAP_LOOP_DONE)
+// for the host's next round.
+FIG_D void fig_cont_publish(FigEng &E, const FigDevBatch &B, const FigKernArgs &A, const FigCont &c) {
+    __threadfence();
+    __syncthreads();
+    if (E.tid == 0) {
+        bool ok = true;
+        if (c.kind == FIG_CONT_EVAL) {
+            const long long live = (long long)gridDim.x - fig_ld_relaxed(&B.cont_hdr->exited);
+            ok = live * 100 >= (long long)c.n * A.cont_live;
+        }
+        if (ok) {
+            const int idx = atomicAdd(&B.cont_hdr->tail, 1);
+            if (idx < B.cont_cap) {
+                FigCont *e = B.cont + idx;
+                e->gap = c.gap; e->j0 = c.j0; e->n = c.n; e->kind = c.kind; e->next = 0; e->rank = c.rank; e->pad = 0;
+                __hip_atomic_store(&e->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                if (c.kind == FIG_CONT_EVAL) atomicAdd(&B.counters[FIG_CNT_CONT], 1ull);
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// Claim one item of the continuations published so far: the entry whose gap has the longest chain of chunks ahead (FIG_CONT_PRIO=0:
+// the oldest), `k` = the item's place in it.  False: a whole scan found nothing to claim.  An entry not yet ready is skipped,
+// not waited for -- its publisher scans after publishing and sees it.  The snapshot of the tail bounds the scan; a claim can be
+// lost only to an entry that is used up from then on, so the scan is repeated at most once per entry.
+FIG_D bool fig_cont_pop(FigEng &E, const FigDevBatch &B, const FigKernArgs &A, FigCont &out, int &k) {
+    FigState &S = *E.S;
+    if (E.tid == 0) { const int t = fig_ld_relaxed(&B.cont_hdr->tail); S.bc_j = t < B.cont_cap ? t : B.cont_cap; }
+    __syncthreads();
+    const int tail = S.bc_j;
+    __syncthreads();
+    for (int pass = 0; pass <= tail; pass++) {      // (each lost claim uses an entry up: at most `tail` of them, then one scan that finds nothing or claims)
+        if (E.tid == 0) S.bc_i = -1;
+        __syncthreads();
+        int best = -1;
+        for (int i = E.tid; i < tail; i += E.nt) {
+            const FigCont *e = B.cont + i;
+            if (!fig_ld_acquire(&e->ready)) continue;
+            if (fig_ld_relaxed(&e->next) >= e->n) continue;
+            const int rank = A.cont_prio ? (e->rank < 32767 ? e->rank : 32767) : 0;
+            const int key = rank * 65536 + (FIG_CONT_CAP_MAX - i);
+            best = key > best ? key : best;
+        }
+        if (best >= 0) atomicMax(&S.bc_i, best);
+        __syncthreads();
+        const int key = S.bc_i;
+        if (key < 0) { __syncthreads(); return false; }
+        const int idx = FIG_CONT_CAP_MAX - (key & 65535);
+        if (E.tid == 0) S.bc_j = atomicAdd(&B.cont[idx].next, 1);
+        __syncthreads();
+        k = S.bc_j;
+        __syncthreads();
+        if (k < B.cont[idx].n) { __threadfence(); out = B.cont[idx]; return true; }
+    }
+    return false;
+}
+
 // ---- kernel 2: speculative candidate evaluations; items = FigItem records (passed as int4 *, like fig_replay_kernel's: the symbols stay)
+// Continuous form (A.cont): the host-planned items first, then whatever the launch's own workgroups publish, until a scan finds nothing.
 static_assert(sizeof(FigItem) == sizeof(int4) && sizeof(FigEntry) == sizeof(int4), "item records travel as int4");
 template <bool LDS_TAB, int NT>
 __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_eval_kernel(FigDevModel M, FigDevBatch B, FigKernArgs A, const int4 *items, int n_items) {
     FigEng E; FigScr work;
     fig_kernel_begin(E, M, B, A, LDS_TAB, work);
     FIG_PROF_BEGIN();
-    fig_pop_loop(E, B, A, [&] { return FigItemSrc<FigItem>{(const FigItem *)items, 0, n_items}; }, [&](FigItem it) { fig_item_eval<LDS_TAB>(E, work, it); });
+    auto eval = [&](FigItem it) {
+        fig_item_eval<LDS_TAB>(E, work, it);
+        if (A.cont && it.chunk > 0 && fig_chunk_finished(E, B, it.gap, it.chunk)) {
+            FigCont nx;
+            fig_item_continue(E, work, it.gap, it.chunk, A.minc, nx);
+            fig_cont_publish(E, B, A, nx);
+        }
+    };
+    fig_pop_loop(E, B, A, [&] { return FigItemSrc<FigItem>{(const FigItem *)items, 0, n_items}; }, eval);
+    if (A.cont) {
+        FigCont c; int k;
+        while (fig_cont_pop(E, B, A, c, k)) {
+            if (c.kind == FIG_CONT_END) fig_item_end<LDS_TAB>(E, work, c.gap);
+            else eval(FigItem{c.gap, c.j0 + k, k, c.n});
+        }
+        if (E.tid == 0) atomicAdd(&B.cont_hdr->exited, 1);
+    }
     FIG_PROF_FLUSH();
     fig_kernel_flush(E, B);
 }
@@ -134,6 +238,10 @@ __global__ void __launch_bounds__(64) fig_replay_kernel(FigDevModel M, FigDevBat
     fig_eng_ident(E, threadIdx.x, blockDim.x, 64);
     E.M = &M; E.B = &B; E.nteams = 1; E.S = (FigState *)fig_lds;
     const FigEntry en = ((const FigEntry *)entries)[blockIdx.x];
+    if (en.stamped) {                    // continuous form: an eval workgroup has replayed every gap that had a chunk; the gap's j has moved on
+        const FigGapCtl c = B.gapctl[en.gap];
+        if (c.status != FIG_GAP_MORE || c.j != en.j_planned || en.n != 0) return;
+    }
     fig_item_replay(E, work, en);
 }
 
@@ -195,7 +303,8 @@ struct FigTmpBufs {
 // queue head, scratch slabs and item buffers, so that the tail of one class's round is filled by the other
 // classes' workgroups.
 struct FigLane { hipStream_t stream = nullptr; hipEvent_t done = nullptr; int32_t *queue_head = nullptr; uint8_t *scratch = nullptr; FigItem *d_items = nullptr; FigEntry *d_entries = nullptr; size_t cap = 0;   // cap: items / entries the buffers hold
-                 FigGapCtl *h_ctl = nullptr; FigItem *h_items = nullptr; FigEntry *h_entries = nullptr; int qsel = 0; };   // h_*: pinned, so the copies run on the DMA engines and never wait for a CU
+                 FigGapCtl *h_ctl = nullptr; FigItem *h_items = nullptr; FigEntry *h_entries = nullptr; int qsel = 0;   // h_*: pinned, so the copies run on the DMA engines and never wait for a CU
+                 uint8_t *d_cont = nullptr; int cont_cap = 0; };   // continuation array of the lane's eval launches: FigContHdr, then cont_cap entries
 
 struct fig_ctx {
     int device = 0;
@@ -220,6 +329,7 @@ struct fig_ctx {
     std::vector<FigLane> lanes;
     fig_stats stats;
     int sh_on = FIG_SH_SC;            // FIG_ESTEP / FIG_SH_CHUNKS, read once at fig_ctx_create
+    FigKnobs fill_knobs;              // the knobs of the fill under way (the lanes' launches read the continuous form's from here)
     std::vector<uint8_t> h_ot;        // host copy of db.ot_preset
     uint8_t *d_ot = nullptr;
 };
@@ -342,7 +452,8 @@ static hipError_t launch_one(void (*k)(P...), size_t lds, int nt, int blocks, hi
 
 template <bool LDS_TAB, int NT>
 static hipError_t launch_kind(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, FigKind kind, int blocks, const void *list, int n, int qsel) {
-    const FigKernArgs A = fig_kargs_of(c.c, qsel, ctx->sh_on);
+    FigKernArgs A = fig_kargs_of(c.c, qsel, ctx->sh_on);
+    if (kind == FIG_K_EVAL) { const FigKnobs &kn = ctx->fill_knobs; A.cont = kn.cont && db.cont_cap > 0; A.minc = kn.minc; A.cont_live = kn.cont_live; A.cont_prio = kn.cont_prio; }
     switch (kind) {
         case FIG_K_FILL: return launch_one(fig_fill_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
         case FIG_K_BEGIN: return launch_one(fig_begin_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
@@ -421,6 +532,7 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     if ((rc = dev_alloc(ctx, (size_t)stride * std::max<size_t>(total_blocks, 1), &p))) return rc; db.scratch = (uint8_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)K.persist_total + 256, &p))) return rc; db.persist = (uint8_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl), &p))) return rc; db.gapctl = (FigGapCtl *)p;
+    if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1) * 4, &p))) return rc; db.gap_pending = (int32_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1), &p))) return rc; ctx->d_ot = (uint8_t *)p; db.ot_preset = ctx->d_ot;
     ctx->h_ot = K.ot_preset;
     FIG_HIP(hipMemcpyAsync(ctx->d_ot, ctx->h_ot.data(), (size_t)std::max<int64_t>(ng, 1), hipMemcpyHostToDevice, ctx->stream));
@@ -436,6 +548,8 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
             l.cap = (size_t)std::max(c.c.q_end - c.c.q_begin, 1) * (size_t)(K.nslots + 1);
             if ((rc = dev_alloc(ctx, l.cap * sizeof(FigItem), &p))) return rc; l.d_items = (FigItem *)p;
             if ((rc = dev_alloc(ctx, l.cap * sizeof(FigEntry), &p))) return rc; l.d_entries = (FigEntry *)p;
+            l.cont_cap = fig_cont_capacity(std::vector<int>(K.order.begin() + c.c.q_begin, K.order.begin() + c.c.q_end), K.gaps, fig_knobs_from_env(0).minc);
+            if ((rc = dev_alloc(ctx, sizeof(FigContHdr) + (size_t)l.cont_cap * sizeof(FigCont), &p))) return rc; l.d_cont = (uint8_t *)p;
             if (hipHostMalloc((void **)&l.h_ctl, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
             if (hipHostMalloc((void **)&l.h_items, l.cap * sizeof(FigItem), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
             if (hipHostMalloc((void **)&l.h_entries, l.cap * sizeof(FigEntry), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
@@ -496,6 +610,9 @@ extern "C" int fig_batch_set_ot_preset(fig_ctx *ctx, const uint8_t *preset) {
 static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln, const FigKnobs &knobs) {
     FigDevBatch db = ctx->db;
     db.queue_head = ln.queue_head; db.scratch = ln.scratch;
+    db.cont_hdr = (FigContHdr *)ln.d_cont; db.cont = (FigCont *)(ln.d_cont + sizeof(FigContHdr));
+    db.cont_cap = knobs.cont ? std::min(ln.cont_cap, knobs.cont_cap) : 0;
+    const size_t cont_bytes = sizeof(FigContHdr) + (size_t)db.cont_cap * sizeof(FigCont);
     hipStream_t stream = ln.stream;
     hipSetDevice(ctx->device);
     int nl = 0;
@@ -524,14 +641,18 @@ static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln, 
         round++;
         if (R.n_active == 0) break;
         if (ln.cap < R.items.size() || ln.cap < R.entries.size()) return fail(hipErrorOutOfMemory);
+        // continuous form: the eval launch replays every gap that has a chunk and goes on with it; the replay launch is left the gaps with nothing to evaluate
+        const int n_empty = knobs.cont ? fig_round_stamp(R, ctl) : 0;
         const int n_items = (int)R.items.size(), n_ent = (int)R.entries.size();
         const size_t items_bytes = R.items.size() * sizeof(FigItem), ent_bytes = R.entries.size() * sizeof(FigEntry);
         last_items = n_items; last_active = R.n_active; last_chunk = R.chunk;
         if (n_items > 0) {
             memcpy(ln.h_items, R.items.data(), items_bytes);
             if ((e = hipMemcpyAsync(ln.d_items, ln.h_items, items_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
+            if (knobs.cont && (e = hipMemsetAsync(ln.d_cont, 0, cont_bytes, stream)) != hipSuccess) return fail(e);
             if ((e = launch(FIG_K_EVAL, n_items, ln.d_items)) != hipSuccess) return fail(e);
         }
+        if (knobs.cont && n_empty == 0) continue;
         memcpy(ln.h_entries, R.entries.data(), ent_bytes);
         if ((e = hipMemcpyAsync(ln.d_entries, ln.h_entries, ent_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return fail(e);
         hipLaunchKernelGGL(fig_replay_kernel, dim3(n_ent), dim3(64), sizeof(FigState) + 64, stream, ctx->dm, db, (const int4 *)ln.d_entries, n_ent);
@@ -577,9 +698,11 @@ extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fi
     FIG_HIP(clear(db.gaptofill, 0, (size_t)std::max<int64_t>(ng, 1) * 4));
     FIG_HIP(clear(db.str, 'N', (size_t)ctx->str_total));
     FIG_HIP(clear(db.gapctl, 0, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl)));
+    FIG_HIP(clear(db.gap_pending, 0, (size_t)std::max<int64_t>(ng, 1) * 4));      // (a lane's continuation array is cleared before each of its eval launches)
     FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     int nl = 0;
     const FigKnobs knobs = fig_knobs_from_env(ctx->dm.unmapped);      // read here, on the caller's thread: the lane threads only get the values
+    ctx->fill_knobs = knobs;
     if (knobs.seq) {
         for (const fig_ctx::Cls &c : ctx->classes) {
             FIG_HIP(clear(db.queue_head, 0, 4));

@@ -136,6 +136,7 @@ static inline void fig_stats_from_counters(const unsigned long long *cnt, fig_st
     st.place_calls = (int64_t)cnt[FIG_CNT_PLACE];
     st.alg_flops = (double)cnt[FIG_CNT_FLOPS]; st.spec_flops = (double)cnt[FIG_CNT_SPEC];
     st.mle_alg_flops = (double)cnt[FIG_CNT_MLE_ALG]; st.mle_exec_flops = (double)cnt[FIG_CNT_MLE_EXEC];
+    st.cont_chunks = (int32_t)cnt[FIG_CNT_CONT];
 }
 
 // the launch arguments of a class (FigKernArgs, fig_engine.h)
@@ -200,6 +201,14 @@ static int fig_fill_gaps_once(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_
 // (the value read at fig_ctx_create).  fig_batch_upload reads `log` for its class listing.
 struct FigKnobs {
     bool seq;            // FIG_SCHED=seq: whole gaps, one workgroup each
+    // FIG_SCHED=rounds: every chunk of every gap is a host round (eval launch + replay launch), the default in partial mode.
+    // FIG_SCHED=continuous, the default in unmapped mode: the
+    // eval launch replays a gap when its chunk is done and continues it in place (fig_engine_sched.h: fig_item_continue); the
+    // host's rounds start the gaps and mop up.  Its knobs: FIG_CONT_CAP=<n> caps the lane's continuation array (tests: 1 forces
+    // the fall-back to host rounds); FIG_CONT_LIVE=<percent> a chunk of n is continued while live workgroups * 100 >= n * percent
+    // (0: always -- one workgroup may then run a whole chain of chunks alone); FIG_CONT_PRIO=0 hands continuations out oldest
+    // first instead of longest remaining chain first
+    bool cont; int cont_cap, cont_live, cont_prio;
     bool lanes_serial;   // FIG_LANES=serial: the class lanes one after the other on the calling thread
     bool log;            // FIG_SCHED_LOG
     int minc;            // FIG_MIN_CHUNK: candidates per gap and round, at least
@@ -214,6 +223,11 @@ static FigKnobs fig_knobs_from_env(int unmapped) {
     const char *sched = getenv("FIG_SCHED"), *ser = getenv("FIG_LANES"), *mc = getenv("FIG_MIN_CHUNK"), *ipw = getenv("FIG_ITEMS_PER_WG");
     const char *ev = getenv("FIG_ESTEP"), *sc = getenv("FIG_SH_CHUNKS");
     k.seq = sched && strcmp(sched, "seq") == 0;
+    const char *cc = getenv("FIG_CONT_CAP"), *cl = getenv("FIG_CONT_LIVE"), *cp = getenv("FIG_CONT_PRIO");
+    k.cont = sched ? strcmp(sched, "continuous") == 0 : unmapped != 0;      // partial mode stays with the rounds: its items take ~1 ms, and the hand-over costs its 8 192-gap pass 15 %
+    k.cont_cap = cc ? std::max(1, atoi(cc)) : FIG_CONT_CAP_MAX;
+    k.cont_live = cl ? std::max(0, atoi(cl)) : 100;
+    k.cont_prio = cp ? (atoi(cp) != 0) : 1;
     k.lanes_serial = ser && strcmp(ser, "serial") == 0;
     k.log = getenv("FIG_SCHED_LOG") != nullptr;
     k.minc = mc ? std::max(1, atoi(mc)) : 16;
@@ -270,6 +284,28 @@ static void fig_plan_round(const std::vector<int> &ids, const FigGapCtl *ctl, in
     // items gap-major in descending-cost gap order (longest processing time first keeps the round's tail short)
     for (const FigEntry &en : R.entries)
         for (int k = en.n - 1; k >= 0; k--) R.items.push_back(FigItem{en.gap, ctl[en.gap].j + k, k, 0});
+}
+
+// The continuous form of a planned round: every item carries the size of its gap's chunk (the workgroup that finishes the
+// chunk's last item replays the gap), every entry the j it was planned at (the replay kernel then takes only the gaps no
+// eval workgroup replayed: those with nothing to evaluate).  Returns the number of such entries.
+static int fig_round_stamp(FigRound &R, const FigGapCtl *ctl) {
+    size_t pos = 0; int n_empty = 0;
+    for (FigEntry &en : R.entries) {
+        en.j_planned = ctl[en.gap].j; en.stamped = 1;
+        if (en.n == 0) n_empty++;
+        for (int k = 0; k < en.n; k++) R.items[pos++].chunk = en.n;
+    }
+    return n_empty;
+}
+
+// Entries of a lane's continuation array: enough for every gap of `ids` to go through its whole range within one launch in chunks
+// of `minc` (FIG_MIN_CHUNK as it stands at upload), plus the end item and the last short chunk.  A fill with a smaller
+// FIG_MIN_CHUNK may find the array full; the gap is then left to the host's next round.
+static int fig_cont_capacity(const std::vector<int> &ids, const std::vector<FigDevGap> &gaps, int minc) {
+    long long n = 0;
+    for (int g : ids) n += gaps[(size_t)g].rangeCap / std::max(1, minc) + 3;
+    return (int)std::min<long long>(std::max<long long>(n, 1), FIG_CONT_CAP_MAX);
 }
 
 #endif

@@ -563,4 +563,35 @@ FIG_D void fig_item_end(FigEng &E, const FigScr &work, int gi) {
     if (E.tid == 0) fig_ctl_of(E, gi).status = FIG_GAP_FINISHED;
     FIG_SYNC();
 }
+
+// ---- the continuous form: a gap goes on inside the eval launch.  The workgroup that finishes the last outstanding item of
+// the gap's chunk replays the gap at once and names what follows (fig_item_continue); the kernel publishes that for any
+// workgroup of the launch (fig_abi.hip), the emulation runs it next.  Nothing here depends on who evaluates what when: the
+// slots of a chunk are replayed in candidate order, exactly as a round's are.
+
+// Candidates of a continued chunk: the size the gap's last chunk had (the planner's share for the gap), at least minc, within
+// the gap's slots and what it has left.
+FIG_HD int fig_cont_chunk(int minc, int last, int slots, int left) {
+    int n = last > minc ? last : minc;
+    if (n > slots) n = slots;
+    if (n > left) n = left;
+    return n;
+}
+
+// After the last item of the gap's chunk of n candidates: the replay, then `next` = the gap's next chunk or its end item.
+// FigCont::rank orders the published continuations: chunks the gap's candidate loop may still need, this one included (the
+// longest chain of chunks is the critical path of a lane); 1 for an end item.
+FIG_D void fig_item_continue(FigEng &E, const FigScr &work, int gi, int n, int minc, FigCont &next) {
+    fig_item_replay(E, work, FigEntry{gi, n, 0, 0});
+    FIG_SYNC();
+    const FigLoop &L = E.S->L;                    // (fig_spec_replay leaves the replayed state in place)
+    next.gap = gi; next.next = 0; next.ready = 0; next.pad = 0;
+    if (L.done) { next.kind = FIG_CONT_END; next.j0 = 0; next.n = 1; next.rank = 1; }
+    else {
+        const int left = L.range - L.j;
+        next.kind = FIG_CONT_EVAL; next.j0 = L.j; next.n = fig_cont_chunk(minc, n, E.g->nslots, left);
+        next.rank = (left + next.n - 1) / (next.n > 0 ? next.n : 1);
+    }
+    FIG_SYNC();
+}
 #endif

@@ -31,14 +31,26 @@ enum { FIG_GAP_FINISHED = 0, FIG_GAP_MORE = 1, FIG_GAP_LOOP_DONE = 2 };   // out
 struct FigGapCtl { int32_t status, j, range, reach; };                    // FIG_GAP_*, next candidate index, candidate count, reach bit of the probe item
 
 // Work items of a round, as the planner lays them out and the kernels read them (one 16-byte load each)
-struct alignas(16) FigItem { int32_t gap, j, slot, pad; };                 // evaluate candidate j of the gap into slot
-struct alignas(16) FigEntry { int32_t gap, n, pad0, pad1; };               // replay the gap's slots 0..n-1
+struct alignas(16) FigItem { int32_t gap, j, slot, chunk; };               // evaluate candidate j of the gap into slot; chunk: see below
+struct alignas(16) FigEntry { int32_t gap, n, j_planned, stamped; };       // replay the gap's slots 0..n-1; the last two: see below
 static_assert(sizeof(FigGapCtl) == 16 && sizeof(FigItem) == 16 && sizeof(FigEntry) == 16, "control words are four int32: buffers and copies are sized by sizeof");
+// Continuous form: FigItem::chunk carries the size of the gap's chunk (0: a round of the rounds form, nobody counts), and
+// FigEntry::j_planned the gap's j when the round was planned, with stamped = 1 (the replay kernel skips a gap an eval workgroup has replayed).
+// A continuation: what the workgroup that replayed a gap's chunk publishes for any workgroup of the launch -- the gap's next
+// chunk (candidates j0 .. j0+n-1 into slots 0 .. n-1) or its end item (n = 1).  Written once, then `ready`; items are claimed
+// by atomicAdd on `next`.  rank: chunks the gap's loop may still need, this one included (1 for an end item): the scan's order.
+enum { FIG_CONT_EVAL = 0, FIG_CONT_END = 1 };
+#define FIG_CONT_CAP_MAX 65535       // entries of a lane's array at most: the scan's keys hold an entry's index in 16 bits
+struct alignas(16) FigCont { int32_t gap, j0, n, kind; int32_t next, ready, rank, pad; };
+// Header of a lane's continuation array (the entries follow it): entries reserved so far; workgroups of the launch that have left.  Zeroed, entries included, before every eval launch
+struct alignas(16) FigContHdr { int32_t tail, exited, pad[2]; };
+static_assert(sizeof(FigCont) == 32 && sizeof(FigContHdr) == 16, "continuation records: buffers are sized by sizeof");
 
 enum FigCounter {                    // slots of FigDevBatch::counters
     FIG_CNT_PLACE = 0,               // placeReads calls of the candidates the gaps' loops consumed
     FIG_CNT_FLOPS = 1, FIG_CNT_SPEC = 2,         // algorithmic flops: useful work only ; every speculative evaluation executed, discarded ones included
     FIG_CNT_MLE_ALG = 3, FIG_CNT_MLE_EXEC = 4,   // MLE passes: flops credited ; FP64 multiplies executed after pruning (raw totals, only their ratio is reported)
+    FIG_CNT_CONT = 5,                // chunks continued inside an eval launch (continuous form)
     // FIG_PROF build: FigEng::prof[i] is counter PROF_LO + i below FIG_PROF_SPLIT, PROF_HI + (i - FIG_PROF_SPLIT) from it on; cycles in barriers; wave-cycles
     FIG_CNT_PROF_LO = 8, FIG_CNT_WAIT = 30, FIG_CNT_WAVE = 31, FIG_CNT_PROF_HI = 32,
     FIG_CNT_N = 64
@@ -108,6 +120,9 @@ struct FigDevBatch {
     int32_t capW, capE;              // weight-buffer doubles, extended-table columns
     uint8_t *persist;                // per-gap persistent slabs
     FigGapCtl *gapctl;               // [n_gaps]
+    // continuous form (null / 0: the rounds form): items of the gap's chunk that have finished, [n_gaps]; the lane's
+    // continuation array, header first, and the entries it holds
+    int32_t *gap_pending; FigContHdr *cont_hdr; FigCont *cont; int32_t cont_cap;
     const uint8_t *ot_preset;        // [n_gaps] 1 = the gap's worker process has set overlap_threshold before it gets to the gap (Figbird.cpp:103, :6317)
     // optional per-base read support (fig_gap_support): the countsGap columns behind the emitted string, [(strOff + x) * 5 + b],
     // and the FIG_ORG_* path mask per gap; both null = off (fig_gap_end takes one uniform branch and stores nothing)

@@ -245,7 +245,7 @@ typedef struct fig_stats {
     int64_t place_calls;                /* placeReads invocations executed on the device     */
     double alg_flops;                   /* algorithmic FP64 flops, counted on device */
     int32_t n_launches;
-    int32_t pad0;
+    int32_t cont_chunks;                /* chunks of candidates continued inside an eval launch (0 under FIG_SCHED=rounds / seq) */
     double spec_flops;                  /* algorithmic flops of every candidate evaluation executed, discarded speculation included */
     double mle_alg_flops;               /* share of the executed evaluations' flops credited to the MLE passes (1 per placement and base) */
     double mle_exec_flops;              /* FP64 multiplies the MLE passes really executed (exact pruning skips the rest) */

@@ -151,8 +151,26 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
             while (true) {
                 fig_plan_round(ids, ctl.data(), 8, c.nsplit, slots_cap, minc, knobs.ipw, n_active_max, R);
                 if (!R.n_active) break;
-                for (const FigItem &it : R.items) { poison(); fig_item_eval<true>(E, work, it); }      // every item starts from poisoned scratch + LDS
-                for (const FigEntry &en : R.entries) { poison(); fig_item_replay(E, work, en); }
+                if (!knobs.cont) {       // FIG_SCHED=rounds: all items of the round, then all replays
+                    for (const FigItem &it : R.items) { poison(); fig_item_eval<true>(E, work, it); }      // every item starts from poisoned scratch + LDS
+                    for (const FigEntry &en : R.entries) { poison(); fig_item_replay(E, work, en); }
+                    continue;
+                }
+                // the continuous order: a gap is replayed as soon as its chunk is done, its next chunk follows at once and its
+                // end item after the last -- the kernel's hand-over with one workgroup, through the same functions
+                fig_round_stamp(R, ctl.data());
+                size_t pos = 0;
+                for (const FigEntry &en : R.entries) {
+                    for (int k = 0; k < en.n; k++) { poison(); fig_item_eval<true>(E, work, R.items[pos++]); }
+                    if (en.n == 0) { poison(); fig_item_replay(E, work, en); continue; }      // (the replay kernel's share)
+                    FigCont nx; nx.n = en.n;
+                    while (true) {
+                        poison(); fig_item_continue(E, work, en.gap, nx.n, minc, nx);
+                        if (nx.kind == FIG_CONT_END) { poison(); fig_item_end<true>(E, work, nx.gap); break; }
+                        counters[FIG_CNT_CONT]++;
+                        for (int k = nx.n - 1; k >= 0; k--) { poison(); fig_item_eval<true>(E, work, FigItem{nx.gap, nx.j0 + k, k, nx.n}); }
+                    }
+                }
             }
             for (int gi : ids) if (ctl[gi].status == FIG_GAP_LOOP_DONE) { poison(); fig_item_end<true>(E, work, gi); }
         }
