@@ -351,6 +351,19 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"{what} failed: {self.lib.fig_strerror(rc).decode()}")
 
+    def _need(self, symbol: str, what: str):
+        if not hasattr(self.lib, symbol):
+            raise RuntimeError(f"{what} needs {symbol}, which this library does not export")
+
+    def _origin_arg(self, what: str, origin):
+        """the `origin` argument of fig_batch_quality / fig_batch_placement -> (the array that keeps it alive, the pointer or None)"""
+        if origin is None:
+            return None, None
+        org = np.ascontiguousarray(origin, dtype=np.int32)
+        if len(org) < self.n_gaps:
+            raise ValueError(f"{what}: one origin per gap of the resident batch")
+        return org, (_p(org, c_i32_p) if len(org) else None)
+
     def set_model(self, model: Model):
         self._model = model
         self._cm = model.cstruct()
@@ -375,8 +388,7 @@ class Engine:
         if not support:
             self._check(self.lib.fig_fill_resident(self.ctx, C.byref(r)), "fig_fill_resident")
             return None, None
-        if not hasattr(self.lib, "fig_fill_resident_ex"):
-            raise RuntimeError("support=True needs fig_fill_resident_ex, which this library does not export")
+        self._need("fig_fill_resident_ex", "support=True")
         sc = np.zeros((max(cap, 1), 5), dtype=np.int32); so = np.zeros(max(n, 1), dtype=np.int32)
         s = FigGapSupport(); s.counts = _p(sc, c_i32_p); s.origin = _p(so, c_i32_p)
         self._check(self.lib.fig_fill_resident_ex(self.ctx, C.byref(r), C.byref(s)), "fig_fill_resident_ex")
@@ -408,15 +420,12 @@ class Engine:
     def placement(self, res: FillResult, origin: Optional[np.ndarray] = None) -> "Placement":
         """fig_batch_placement of the strings and draw planes in `res` against the resident batch; `origin` as for quality().
         The buffers handed to the library start as 0xFF bytes, so that an element it failed to write shows."""
-        if not hasattr(self.lib, "fig_batch_placement"):
-            raise RuntimeError("placement needs fig_batch_placement, which this library does not export")
+        self._need("fig_batch_placement", "placement")
         r, keep = self._filled_struct("placement", res)
         n, nu = self.n_gaps, self._n_ureads()
         if len(keep[3]) < nu:
             raise ValueError("placement: one drawn offset per unmapped read of the resident batch")
-        org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-        if org is not None and len(org) < n:
-            raise ValueError("placement: one origin per gap of the resident batch")
+        org, org_p = self._origin_arg("placement", origin)
         m = max(nu, 1)
         d = [np.zeros(m) for _ in range(3)]
         for a in d:
@@ -426,7 +435,7 @@ class Engine:
         rp = FigReadPlacement()
         rp.ll_drawn = _p(d[0], c_double_p); rp.ll_other = _p(d[1], c_double_p); rp.sum_other = _p(d[2], c_double_p)
         rp.off_other = _p(off, c_i32_p); rp.n_valid = _p(nv, c_i32_p); rp.pq = _p(pq, c_u8_p); rp.state = _p(stt, c_u8_p)
-        self._check(self.lib.fig_batch_placement(self.ctx, C.byref(r), None if org is None or not len(org) else _p(org, c_i32_p), C.byref(rp)), "fig_batch_placement")
+        self._check(self.lib.fig_batch_placement(self.ctx, C.byref(r), org_p, C.byref(rp)), "fig_batch_placement")
         return Placement(d[0][:nu], d[1][:nu], d[2][:nu], off[:nu], nv[:nu], pq[:nu], stt[:n])
 
     def quality(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: Optional["Placement"] = None, min_pq: Optional[int] = None):
@@ -443,46 +452,56 @@ class Engine:
             drop = np.flatnonzero((pq != PLACE_NONE) & (pq < min_pq))
             dpos[drop] = np.iinfo(np.int32).min
             res = dc_replace(res, draw=(dpos, res.draw[1], res.draw[2]))
-        if not hasattr(self.lib, "fig_batch_quality"):
-            raise RuntimeError("quality needs fig_batch_quality, which this library does not export")
-        if res.draw is None:
-            raise ValueError("quality: the fill result carries no draw planes (fill with draw=True)")
+        self._need("fig_batch_quality", "quality")
+        r, keep = self._filled_struct("quality", res)
         n = self.n_gaps
-        fl = np.ascontiguousarray(res.filled_len, dtype=np.int32); so = np.ascontiguousarray(res.str_off, dtype=np.int64)
-        if len(fl) < n or len(so) < n + 1:
-            raise ValueError("quality: one length and one offset per gap of the resident batch")
-        fl = fl if n else np.zeros(1, dtype=np.int32)
-        total = int(so[n])
-        raw = np.ascontiguousarray(res.raw, dtype=np.uint8) if res.raw is not None and len(res.raw) else np.zeros(1, dtype=np.uint8)
-        dpos, disz, dlen = (np.ascontiguousarray(a, dtype=np.int32) for a in res.draw)
-        dpos, disz, dlen = (a if len(a) else np.zeros(1, dtype=np.int32) for a in (dpos, disz, dlen))
-        r = FigGapResults()
-        r.filled_len = _p(fl, c_i32_p); r.str_off = _p(so, c_i64_p); r.str = C.cast(raw.ctypes.data, C.c_char_p); r.str_capacity = len(raw)
-        r.draw_pos = _p(dpos, c_i32_p); r.draw_isz = _p(disz, c_i32_p); r.draw_len = _p(dlen, c_i32_p)
-        org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-        if org is not None and len(org) < n:
-            raise ValueError("quality: one origin per gap of the resident batch")
+        total = int(keep[1][n])
+        org, org_p = self._origin_arg("quality", origin)
         ll = np.full((max(total, 1), 4), np.nan); ll.view(np.uint8)[...] = 0xFF
         ph = np.full(max(total, 1), 0xFF, dtype=np.uint8); stt = np.full(max(n, 1), 0xFF, dtype=np.uint8)
         gq = FigGapQuality(); gq.loglik = _p(ll, c_double_p); gq.phred = _p(ph, c_u8_p); gq.state = _p(stt, c_u8_p)
-        self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), None if org is None or not len(org) else _p(org, c_i32_p), C.byref(gq)), "fig_batch_quality")
+        self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), org_p, C.byref(gq)), "fig_batch_quality")
         return ll[:total], ph[:total], stt[:n]
+
+    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool):
+        """quality and placement need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+        if quality:
+            self._need("fig_batch_quality", "quality=True")
+        if placement:
+            self._need("fig_batch_placement", "placement=True")
+        return draw or quality or placement, support or quality or placement
+
+    def _result_arrays(self, n: int, cap: int, nr: Optional[int], draw: bool):
+        """Fresh result arrays for n gaps and cap string bytes and, unless nr is None, draw planes for nr reads, behind a
+        fig_gap_results that carries the planes iff `draw` -> (r, filled_len, gaptofill, str_off, str, planes or None)"""
+        fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
+        so = np.zeros(n + 1, dtype=np.int64); st = np.zeros(max(cap, 1), dtype=np.uint8)
+        r = FigGapResults()
+        r.filled_len = _p(fl, c_i32_p); r.gaptofill = _p(gt, c_i32_p); r.str_off = _p(so, c_i64_p)
+        r.str = C.cast(st.ctypes.data, C.c_char_p); r.str_capacity = len(st)
+        planes = None
+        if nr is not None:
+            planes = (np.full(max(nr, 1), np.iinfo(np.int32).min, dtype=np.int32), np.zeros(max(nr, 1), dtype=np.int32), np.full(max(2 * n, 1), -1, dtype=np.int32))
+        if draw:
+            r.draw_pos = _p(planes[0], c_i32_p); r.draw_isz = _p(planes[1], c_i32_p); r.draw_len = _p(planes[2], c_i32_p)
+        return r, fl, gt, so, st, planes
+
+    def _post_fill(self, filled: FillResult, placement: bool, quality: bool, min_pq: Optional[int] = None):
+        """the passes beside a fill whose batch is still resident, with its origins -> (Placement or None, quality or None)"""
+        plc = self.placement(filled, filled.support_origin) if placement else None
+        qual = None
+        if quality:
+            qual = self.quality(filled, filled.support_origin, placement=plc if min_pq is not None else None, min_pq=min_pq)
+        return plc, qual
 
     def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
                       placement: bool = False) -> FillResult:
         """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins);
         placement=True likewise fills FillResult.placement (fig_batch_placement with the origins)."""
-        if quality and not hasattr(self.lib, "fig_batch_quality"):
-            raise RuntimeError("quality=True needs fig_batch_quality, which this library does not export")
-        if placement and not hasattr(self.lib, "fig_batch_placement"):
-            raise RuntimeError("placement=True needs fig_batch_placement, which this library does not export")
-        draw = draw or quality or placement; support = support or quality or placement
+        draw, support = self._implied(support, draw, quality, placement)
         n = self.n_gaps
-        fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
-        so = np.zeros(n + 1, dtype=np.int64); st = np.zeros(max(self.cap, 1), dtype=np.uint8)
-        r = FigGapResults()
-        r.filled_len = _p(fl, c_i32_p); r.gaptofill = _p(gt, c_i32_p); r.str_off = _p(so, c_i64_p)
-        r.str = C.cast(st.ctypes.data, C.c_char_p); r.str_capacity = len(st)
+        nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1]) if draw else None
+        r, fl, gt, so, st, planes = self._result_arrays(n, self.cap, nr, draw)
         if debug_cand > 0:
             dn = np.zeros(max(n, 1), dtype=np.int32); di = np.zeros(max(n, 1) * debug_cand * 3, dtype=np.int32)
             dl = np.zeros(max(n, 1) * debug_cand)
@@ -494,11 +513,6 @@ class Engine:
             if plane_reads > 0:
                 pr = np.zeros((max(n, 1), debug_cand, plane_reads))
                 r.dbg_plane_reads = plane_reads; r.dbg_read_maxlv = _p(pr, c_double_p)
-        if draw:
-            nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1])
-            dpos = np.full(max(nr, 1), np.iinfo(np.int32).min, dtype=np.int32); disz = np.zeros(max(nr, 1), dtype=np.int32)
-            dlen = np.full(max(2 * n, 1), -1, dtype=np.int32)
-            r.draw_pos = _p(dpos, c_i32_p); r.draw_isz = _p(disz, c_i32_p); r.draw_len = _p(dlen, c_i32_p)
         sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
         raw = st.tobytes()
         strings = [raw[so[g]:so[g + 1]].decode() for g in range(n)]
@@ -516,13 +530,10 @@ class Engine:
         if debug_cand > 0 and plane_reads > 0:
             res.read_maxlv = pr[:n]
         if draw:
-            res.draw = (dpos[:nr], disz[:nr], dlen[:2 * n])
+            res.draw = (planes[0][:nr], planes[1][:nr], planes[2][:2 * n])
         if support:
             res.support = sup_c[:int(so[n])]; res.support_origin = sup_o[:n]
-        if placement:
-            res.placement = self.placement(res, res.support_origin)
-        if quality:
-            res.quality = self.quality(res, res.support_origin)
+        res.placement, res.quality = self._post_fill(res, placement, quality)
         return res
 
     def free_batch(self):
@@ -560,41 +571,25 @@ class Engine:
         fig_batch_quality before the batch is freed (field `quality`).  keep_resident=True leaves an uploaded batch resident
         for a further call.  placement=True likewise runs fig_batch_placement (field `placement`); with min_pq as well the
         quality leaves out the scored reads below that pq (Engine.quality)."""
-        if quality and not hasattr(self.lib, "fig_batch_quality"):
-            raise RuntimeError("quality=True needs fig_batch_quality, which this library does not export")
+        draw, support = self._implied(support, draw, quality, placement or min_pq is not None)
         placement = placement or min_pq is not None
-        if placement and not hasattr(self.lib, "fig_batch_placement"):
-            raise RuntimeError("placement=True needs fig_batch_placement, which this library does not export")
-        draw = draw or quality or placement; support = support or quality or placement
         qual = plc = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
-        fl = np.zeros(max(n, 1), dtype=np.int32); gt = np.zeros(max(n, 1), dtype=np.int32)
-        so = np.zeros(n + 1, dtype=np.int64); st = np.zeros(max(cap, 1), dtype=np.uint8)
-        r = FigGapResults()
-        r.filled_len = _p(fl, c_i32_p); r.gaptofill = _p(gt, c_i32_p); r.str_off = _p(so, c_i64_p)
-        r.str = C.cast(st.ctypes.data, C.c_char_p); r.str_capacity = len(st)
         nr = n_ureads + n_preads
-        dpos = np.full(max(nr, 1), np.iinfo(np.int32).min, dtype=np.int32); disz = np.zeros(max(nr, 1), dtype=np.int32)
-        dlen = np.full(max(2 * n, 1), -1, dtype=np.int32)
-        if draw:
-            r.draw_pos = _p(dpos, c_i32_p); r.draw_isz = _p(disz, c_i32_p); r.draw_len = _p(dlen, c_i32_p)
+        r, fl, gt, so, st, (dpos, disz, dlen) = self._result_arrays(n, cap, nr, draw)
         sup_c = sup_o = None
-        if support and not hasattr(self.lib, "fig_fill_resident_ex"):
-            raise RuntimeError("support=True needs fig_fill_resident_ex, which this library does not export")
+        if support:
+            self._need("fig_fill_resident_ex", "support=True")
         if n > 0 and not resident and support:            # (fig_fill_gaps has no support argument: upload, then the resident call)
             self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
             resident = True
         if n > 0 and resident:
             try:
                 sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
-                if placement:
+                if placement or quality:
                     self.n_gaps = n; self._cb = cbatch
-                    plc = self.placement(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen)), sup_o)
-                if quality:
-                    self.n_gaps = n
-                    qual = self.quality(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen)), sup_o,
-                                        placement=plc if min_pq is not None else None, min_pq=min_pq)
+                    plc, qual = self._post_fill(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), placement, quality, min_pq)
             finally:
                 if not keep_resident:
                     self.lib.fig_batch_free(self.ctx)

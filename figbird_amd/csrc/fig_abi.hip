@@ -759,27 +759,76 @@ extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fi
     return rc;
 }
 
-// Per-base quality of a fill's strings (fig_quality.h: the kernel; fig_quality_host.h: tables, Phred, which gaps are on).  Beside
-// the fill: per-call device buffers, the library's stream, nothing of the resident batch or the model is written.
+// What the two passes beside the fill, fig_batch_quality and fig_batch_placement, do alike: per-call device buffers, the library's
+// stream, nothing of the resident batch or the model is written.  open() checks the context and the caller's strings and fetches
+// what the host needs; up() / alloc() own the device buffers; run() is the event-timed launch and the way back.
+struct FigPostFill {
+    fig_ctx *ctx = nullptr;
+    const fig_gap_results *f = nullptr;
+    int64_t total = 0;                         // bytes of the caller's strings
+    std::vector<FigDevGap> hg;                 // the gap descriptors (read ranges, anchors)
+    std::vector<double> tabs;                  // lm[L] | le[L] | lt[16] of the model's e[k] / 1 - e[k] as the device holds them
+    FigTmpBufs tmp;
+    bool oom = false;
+    float ms = 0;
+
+    int open(fig_ctx *c, const fig_gap_results *filled, std::vector<double> *insd = nullptr) {      // insd: the insert-size table as well
+        ctx = c; f = filled;
+        if (!ctx || !f || !ctx->have_batch || !ctx->have_model) return FIG_EINVAL;
+        if (!f->filled_len || !f->str_off || !f->draw_pos || !f->draw_len) return FIG_EINVAL;
+        hipSetDevice(ctx->device);
+        const int64_t ng = ctx->n_gaps;
+        if (f->str_off[0] < 0) return FIG_EINVAL;
+        for (int64_t g = 0; g < ng; g++) if (f->str_off[g + 1] < f->str_off[g]) return FIG_EINVAL;
+        total = f->str_off[ng];
+        if (total > 0 && !f->str) return FIG_EINVAL;
+        const int L = ctx->dm.L;
+        hg.resize((size_t)ng);
+        std::vector<double> he((size_t)L), home((size_t)L);
+        tabs.resize((size_t)fig_quality_tab_doubles(L));
+        if (ng > 0) FIG_HIP(fetch(hg.data(), ctx->db.gaps, (size_t)ng * sizeof(FigDevGap)));
+        FIG_HIP(fetch(he.data(), ctx->dm.e, (size_t)L * sizeof(double)));
+        FIG_HIP(fetch(home.data(), ctx->dm.ome1, (size_t)L * sizeof(double)));
+        if (insd) { insd->resize((size_t)ctx->dm.max_insert); FIG_HIP(fetch(insd->data(), ctx->dm.insd, insd->size() * sizeof(double))); }
+        FIG_HIP(hipStreamSynchronize(ctx->stream));
+        fig_quality_tables(L, he.data(), home.data(), ctx->dm.T, tabs.data(), tabs.data() + L, tabs.data() + 2 * L);
+        return FIG_OK;
+    }
+    // A gap that is on, its string of n bytes and its reads base .. base + cnt - 1 of `limit`: how many of them are drawn, or -1
+    // where the caller's offsets or draw plane do not hold what the kernel will index with
+    int64_t drawn_reads(int64_t g, int32_t n, int64_t base, int64_t cnt, int64_t limit) const {
+        if (n > (1 << 30) || f->str_off[g] + n > f->str_off[g + 1] || base < 0 || cnt < 0 || base + cnt > limit) return -1;
+        return fig_quality_check_placements(f->draw_pos + base, cnt);
+    }
+    hipError_t fetch(void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream); }
+    void *alloc(size_t bytes) { void *p = tmp.alloc(bytes); oom = oom || !p; return p; }
+    template <typename T> const T *up(const T *src, size_t count) {
+        void *p = alloc(count * sizeof(T));
+        if (p && count && hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { oom = true; return nullptr; }
+        return (const T *)p;
+    }
+    // the launch between the context's two events, then `back` (the copies to the host) and the wait; FIG_ENOMEM if an up() / alloc() failed
+    template <typename Launch, typename Back> int run(Launch launch, Back back) {
+        if (oom) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
+        FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        launch();
+        FIG_HIP(hipGetLastError());
+        FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        FIG_HIP(back());
+        FIG_HIP(hipStreamSynchronize(ctx->stream));
+        FIG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        return FIG_OK;
+    }
+};
+#define FIG_TRY(call) do { const int _rc = (call); if (_rc != FIG_OK) return _rc; } while (0)
+
+// Per-base quality of a fill's strings (fig_quality.h: the kernel; fig_quality_host.h: tables, Phred, which gaps are on)
 extern "C" int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_quality *q) {
-    if (!ctx || !f || !q || !ctx->have_batch || !ctx->have_model) return FIG_EINVAL;
-    if (!f->filled_len || !f->str_off || !f->draw_pos || !f->draw_isz || !f->draw_len || !q->loglik || !q->phred || !q->state) return FIG_EINVAL;
-    hipSetDevice(ctx->device);
-    const int64_t ng = ctx->n_gaps, nr = ctx->n_ureads + ctx->n_preads;
-    if (f->str_off[0] < 0) return FIG_EINVAL;
-    for (int64_t g = 0; g < ng; g++) if (f->str_off[g + 1] < f->str_off[g]) return FIG_EINVAL;
-    const int64_t total = f->str_off[ng];
-    if (total > 0 && !f->str) return FIG_EINVAL;
+    if (!q || !q->loglik || !q->phred || !q->state || (f && !f->draw_isz)) return FIG_EINVAL;
+    FigPostFill P;
+    FIG_TRY(P.open(ctx, f));
+    const int64_t ng = ctx->n_gaps, total = P.total, nr = ctx->n_ureads + ctx->n_preads;
     const FigDevBatch &db = ctx->db;
-    const int L = ctx->dm.L;
-    // the gap descriptors (read ranges) and the model's e[k] / 1 - e[k] as the device holds them
-    std::vector<FigDevGap> hg((size_t)ng);
-    std::vector<double> he((size_t)L), home((size_t)L), tabs((size_t)fig_quality_tab_doubles(L));
-    if (ng > 0) FIG_HIP(hipMemcpyAsync(hg.data(), db.gaps, (size_t)ng * sizeof(FigDevGap), hipMemcpyDeviceToHost, ctx->stream));
-    FIG_HIP(hipMemcpyAsync(he.data(), ctx->dm.e, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FIG_HIP(hipMemcpyAsync(home.data(), ctx->dm.ome1, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FIG_HIP(hipStreamSynchronize(ctx->stream));
-    fig_quality_tables(L, he.data(), home.data(), ctx->dm.T, tabs.data(), tabs.data() + L, tabs.data() + 2 * L);
     // which gaps are on, and the bounds of what the kernel will index with
     std::vector<int32_t> list, ncol((size_t)std::max<int64_t>(ng, 1), 0);
     std::vector<uint8_t> part((size_t)std::max<int64_t>(ng, 1), 0);
@@ -788,75 +837,48 @@ extern "C" int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *f, const i
         const int32_t n = f->filled_len[g], lu = f->draw_len[2 * g], lp = f->draw_len[2 * g + 1];
         q->state[g] = fig_quality_gap_on(n, lu, lp, origin != nullptr, origin ? origin[g] : 0);
         if (q->state[g] != FIG_QUAL_ON) continue;
-        if (n > (1 << 30) || f->str_off[g] + n > f->str_off[g + 1]) return FIG_EINVAL;
         const bool p = lp >= 0;
-        const int64_t base = p ? ctx->n_ureads + hg[(size_t)g].pBase : hg[(size_t)g].uBase, cnt = p ? hg[(size_t)g].nP : hg[(size_t)g].nU;
-        if (base < 0 || cnt < 0 || base + cnt > nr) return FIG_EINVAL;
-        const int64_t drawn = fig_quality_check_placements(f->draw_pos + base, cnt);
+        const int64_t base = p ? ctx->n_ureads + P.hg[(size_t)g].pBase : P.hg[(size_t)g].uBase, cnt = p ? P.hg[(size_t)g].nP : P.hg[(size_t)g].nU;
+        const int64_t drawn = P.drawn_reads(g, n, base, cnt, nr);
         if (drawn < 0) return FIG_EINVAL;
         list.push_back((int32_t)g); ncol[(size_t)g] = n; part[(size_t)g] = p ? 1 : 0;
         cols += n; reads += drawn;
     }
-    float ms = 0;
     if (total > 0) memset(q->loglik, 0, (size_t)total * 4 * sizeof(double));
     if (total > 0) memset(q->phred, 0, (size_t)total);
     if (!list.empty()) {
-        FigTmpBufs tmp;
-        auto up = [&](const void *src, size_t bytes) -> void * {
-            void *p = tmp.alloc(bytes);
-            if (p && bytes && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
-            return p;
-        };
         FigQualArgs A;
         A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.p_len = db.p.len; A.u_woff = db.u.woff; A.p_woff = db.p.woff;
-        A.packed = db.packed; A.n_ureads = ctx->n_ureads; A.L = L;
-        A.draw_pos = (const int32_t *)up(f->draw_pos, (size_t)nr * 4);
-        A.list = (const int32_t *)up(list.data(), list.size() * 4);
-        A.ncol = (const int32_t *)up(ncol.data(), (size_t)ng * 4);
-        A.partial = (const uint8_t *)up(part.data(), (size_t)ng);
-        A.str_off = (const int64_t *)up(f->str_off, (size_t)(ng + 1) * 8);
-        A.tabs = (const double *)up(tabs.data(), tabs.size() * sizeof(double));
-        A.loglik = (double *)tmp.alloc((size_t)total * 4 * sizeof(double));
-        if (!A.draw_pos || !A.list || !A.ncol || !A.partial || !A.str_off || !A.tabs || !A.loglik) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
-        FIG_HIP(hipMemsetAsync(A.loglik, 0, (size_t)total * 4 * sizeof(double), ctx->stream));
-        FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-        hipLaunchKernelGGL(fig_quality_kernel, dim3((unsigned)list.size()), dim3(FIG_Q_NT), 0, ctx->stream, A);
-        FIG_HIP(hipGetLastError());
-        FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-        FIG_HIP(hipMemcpyAsync(q->loglik, A.loglik, (size_t)total * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        FIG_HIP(hipStreamSynchronize(ctx->stream));
-        FIG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        A.packed = db.packed; A.n_ureads = ctx->n_ureads; A.L = ctx->dm.L;
+        A.draw_pos = P.up(f->draw_pos, (size_t)nr);
+        A.list = P.up(list.data(), list.size());
+        A.ncol = P.up(ncol.data(), (size_t)ng);
+        A.partial = P.up(part.data(), (size_t)ng);
+        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
+        A.tabs = P.up(P.tabs.data(), P.tabs.size());
+        A.loglik = (double *)P.alloc((size_t)total * 4 * sizeof(double));
+        if (A.loglik) FIG_HIP(hipMemsetAsync(A.loglik, 0, (size_t)total * 4 * sizeof(double), ctx->stream));
+        FIG_TRY(P.run([&] { hipLaunchKernelGGL(fig_quality_kernel, dim3((unsigned)list.size()), dim3(FIG_Q_NT), 0, ctx->stream, A); },
+                      [&] { return P.fetch(q->loglik, A.loglik, (size_t)total * 4 * sizeof(double)); }));
     }
     for (int32_t g : list)
         for (int64_t i = f->str_off[g], e = f->str_off[g] + ncol[(size_t)g]; i < e; i++) q->phred[i] = fig_quality_phred(q->loglik + i * 4, f->str[i]);
     if (fig_knobs_from_env(ctx->dm.unmapped).log)
-        fprintf(stderr, "[figqual] gaps on %zu of %lld, columns %lld, reads %lld, kernel %.3f ms\n", list.size(), (long long)ng, (long long)cols, (long long)reads, ms);
+        fprintf(stderr, "[figqual] gaps on %zu of %lld, columns %lld, reads %lld, kernel %.3f ms\n", list.size(), (long long)ng, (long long)cols, (long long)reads, P.ms);
     return FIG_OK;
 }
 
 // Placement confidence per drawn unmapped read (fig_placement.h: the kernel; fig_placement_host.h: li, insert size, validity, which
-// gaps are on, Phred).  Beside the fill like fig_batch_quality: per-call device buffers, the library's stream, nothing of the
-// resident batch or the model is written.
+// gaps are on, Phred)
 extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_read_placement *p) {
-    if (!ctx || !f || !p || !ctx->have_batch || !ctx->have_model) return FIG_EINVAL;
-    if (!f->filled_len || !f->str_off || !f->draw_pos || !f->draw_len) return FIG_EINVAL;
-    if (!p->ll_drawn || !p->ll_other || !p->sum_other || !p->off_other || !p->n_valid || !p->pq || !p->state) return FIG_EINVAL;
-    hipSetDevice(ctx->device);
+    if (!p || !p->ll_drawn || !p->ll_other || !p->sum_other || !p->off_other || !p->n_valid || !p->pq || !p->state) return FIG_EINVAL;
+    FigPostFill P;
+    std::vector<double> insd;
+    FIG_TRY(P.open(ctx, f, &insd));
     const int64_t ng = ctx->n_gaps, nu = ctx->n_ureads;
-    if (f->str_off[0] < 0) return FIG_EINVAL;
-    for (int64_t g = 0; g < ng; g++) if (f->str_off[g + 1] < f->str_off[g]) return FIG_EINVAL;
-    const int64_t total = f->str_off[ng];
-    if (total > 0 && !f->str) return FIG_EINVAL;
     const FigDevBatch &db = ctx->db;
-    const int L = ctx->dm.L, MI = ctx->dm.max_insert;
-    std::vector<FigDevGap> hg((size_t)ng);
-    std::vector<double> he((size_t)L), home((size_t)L), tabs((size_t)fig_quality_tab_doubles(L)), insd((size_t)MI), li((size_t)MI);
-    if (ng > 0) FIG_HIP(hipMemcpyAsync(hg.data(), db.gaps, (size_t)ng * sizeof(FigDevGap), hipMemcpyDeviceToHost, ctx->stream));
-    FIG_HIP(hipMemcpyAsync(he.data(), ctx->dm.e, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FIG_HIP(hipMemcpyAsync(home.data(), ctx->dm.ome1, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FIG_HIP(hipMemcpyAsync(insd.data(), ctx->dm.insd, (size_t)MI * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FIG_HIP(hipStreamSynchronize(ctx->stream));
-    fig_quality_tables(L, he.data(), home.data(), ctx->dm.T, tabs.data(), tabs.data() + L, tabs.data() + 2 * L);
+    const int MI = ctx->dm.max_insert;
+    std::vector<double> li((size_t)MI);
     fig_placement_li(MI, insd.data(), li.data());
     // which gaps are on, their work items, and the bounds of what the kernel will index with
     std::vector<int32_t> items;
@@ -867,54 +889,38 @@ extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const
         const int32_t n = f->filled_len[g];
         p->state[g] = fig_placement_gap_on(ctx->dm.unmapped != 0, n, f->draw_len[2 * g], f->draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
         if (p->state[g] != FIG_PLACE_ON) continue;
-        if (n > (1 << 30) || f->str_off[g] + n > f->str_off[g + 1]) return FIG_EINVAL;
-        const int64_t base = hg[(size_t)g].uBase, cnt = hg[(size_t)g].nU;
-        if (base < 0 || cnt < 0 || base + cnt > nu) return FIG_EINVAL;
-        const int64_t drawn = fig_placement_check_offsets(f->draw_pos + base, cnt);
+        const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
+        const int64_t drawn = P.drawn_reads(g, n, base, cnt, nu);
         if (drawn < 0) return FIG_EINVAL;
         gaps_on++; ncol[(size_t)g] = n; reads += drawn;
         for (int64_t r = 0; r < cnt; r++) scored[(size_t)(base + r)] = f->draw_pos[base + r] != INT32_MIN;
-        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_P_CHUNK) {               // a chunk without a drawn read is no work item
+        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {              // a chunk without a drawn read is no work item
             bool any = false;
-            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_P_CHUNK, cnt); r++) any = any || scored[(size_t)(base + r)];
+            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) any = any || scored[(size_t)(base + r)];
             if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
         }
     }
     for (int64_t r = 0; r < nu; r++) {
         p->ll_drawn[r] = 0.0; p->ll_other[r] = 0.0; p->sum_other[r] = 0.0; p->off_other[r] = INT32_MIN; p->n_valid[r] = 0; p->pq[r] = FIG_PLACE_NONE;
     }
-    float ms = 0;
     if (!items.empty()) {
-        FigTmpBufs tmp;
-        auto up = [&](const void *src, size_t bytes) -> void * {
-            void *q = tmp.alloc(bytes);
-            if (q && bytes && hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
-            return q;
-        };
         FigPlaceArgs A;
         A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_pos = db.u.pos; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank;
-        A.L = L; A.Tmin = ctx->dm.Tmin; A.Tmax = ctx->dm.Tmax; A.max_insert = MI;
-        A.draw_pos = (const int32_t *)up(f->draw_pos, (size_t)nu * 4);
-        A.items = (const int32_t *)up(items.data(), items.size() * 4);
-        A.ncol = (const int32_t *)up(ncol.data(), (size_t)ng * 4);
-        A.str_off = (const int64_t *)up(f->str_off, (size_t)(ng + 1) * 8);
-        A.str = (const char *)up(f->str, (size_t)total);
-        A.tabs = (const double *)up(tabs.data(), tabs.size() * sizeof(double));
-        A.li = (const double *)up(li.data(), li.size() * sizeof(double));
-        double *dd = (double *)tmp.alloc((size_t)nu * 3 * sizeof(double));
-        int32_t *di = (int32_t *)tmp.alloc((size_t)nu * 2 * sizeof(int32_t));
-        if (!A.draw_pos || !A.items || !A.ncol || !A.str_off || !A.str || !A.tabs || !A.li || !dd || !di) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
+        A.L = ctx->dm.L; A.Tmin = ctx->dm.Tmin; A.Tmax = ctx->dm.Tmax; A.max_insert = MI;
+        A.draw_pos = P.up(f->draw_pos, (size_t)nu);
+        A.items = P.up(items.data(), items.size());
+        A.ncol = P.up(ncol.data(), (size_t)ng);
+        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
+        A.str = P.up(f->str, (size_t)P.total);
+        A.tabs = P.up(P.tabs.data(), P.tabs.size());
+        A.li = P.up(li.data(), li.size());
+        double *dd = (double *)P.alloc((size_t)nu * 3 * sizeof(double));
+        int32_t *di = (int32_t *)P.alloc((size_t)nu * 2 * sizeof(int32_t));
         A.ll_drawn = dd; A.ll_other = dd + nu; A.sum_other = dd + 2 * nu; A.off_other = di; A.n_valid = di + nu;
         std::vector<double> hd((size_t)nu * 3);
         std::vector<int32_t> hi((size_t)nu * 2);
-        FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-        hipLaunchKernelGGL(fig_placement_kernel, dim3((unsigned)(items.size() / 2)), dim3(FIG_P_NT), 0, ctx->stream, A);
-        FIG_HIP(hipGetLastError());
-        FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-        FIG_HIP(hipMemcpyAsync(hd.data(), dd, hd.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        FIG_HIP(hipMemcpyAsync(hi.data(), di, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        FIG_HIP(hipStreamSynchronize(ctx->stream));
-        FIG_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+        FIG_TRY(P.run([&] { hipLaunchKernelGGL(fig_placement_kernel, dim3((unsigned)(items.size() / 2)), dim3(FIG_P_NT), 0, ctx->stream, A); },
+                      [&] { const hipError_t e = P.fetch(hd.data(), dd, hd.size() * sizeof(double)); return e != hipSuccess ? e : P.fetch(hi.data(), di, hi.size() * sizeof(int32_t)); }));
         for (int64_t r = 0; r < nu; r++) {
             if (!scored[(size_t)r]) continue;
             p->ll_drawn[r] = hd[(size_t)r]; p->ll_other[r] = hd[(size_t)(nu + r)]; p->sum_other[r] = hd[(size_t)(2 * nu + r)];
@@ -924,7 +930,7 @@ extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const
         }
     }
     if (fig_knobs_from_env(ctx->dm.unmapped).log)
-        fprintf(stderr, "[figplace] gaps on %lld of %lld, reads scored %lld, placements scored %lld, kernel %.3f ms\n", (long long)gaps_on, (long long)ng, (long long)reads, (long long)placements, ms);
+        fprintf(stderr, "[figplace] gaps on %lld of %lld, reads scored %lld, placements scored %lld, kernel %.3f ms\n", (long long)gaps_on, (long long)ng, (long long)reads, (long long)placements, P.ms);
     return FIG_OK;
 }
 

@@ -10,18 +10,11 @@
 #define FIG_PLACEMENT_H
 #include <stdint.h>
 #include "fig_placement_host.h"
+#include "fig_readstage.h"
 
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-#include "fig_types.h"
-#endif
-
-#define FIG_P_NT 256                 // threads of a workgroup = offsets of a tile (four waves of 64)
-#define FIG_P_CHUNK 64               // reads of a work item
-#define FIG_P_WORDS 20               // dwords of a staged read: ceil(200/16) 2-bit words + ceil(200/32) N-mask words (pack_read, fig_pack.h)
-#define FIG_P_MAXL 200               // FIG_MAX_READLEN
-#define FIG_P_FLANK 208              // FIG_FLANK
-#define FIG_P_WIN (FIG_P_NT + FIG_P_MAXL - 1)        // columns a tile's placements touch
+#define FIG_P_NT (4 * FIG_RS_CHUNK)  // threads of a workgroup = offsets of a tile (four waves of 64); a work item is one chunk of reads
+#define FIG_P_FLANK FIG_FLANK       // flank codes kept either side of a gap (fig_types.h)
+#define FIG_P_WIN (FIG_P_NT + FIG_RS_MAXL - 1)       // columns a tile's placements touch
 #define FIG_P_LQ (-0x1.34413509f79ffp-1)             // log10(1/4): an N column under a uniform prior over its base
 
 // Column x of the gap's sequence as a code 0..4 (A C G T N): flank codes left of the string and right of it (fl[k-1] = column -k,
@@ -39,11 +32,9 @@ FIG_P_HD inline int fig_placement_column(int x, int n, FP fl, SP str) {
 // lt: log10(T[column][read]) as [column * 4 + read].
 template <typename SP, typename WP, typename DP>
 FIG_P_HD inline double fig_placement_score(double lr, SP S, int len, int rev, WP w, DP lm, DP le, DP lt) {
-    const int nw2 = (len + 15) >> 4;
     for (int j = 0; j < len; j++) {
-        if ((w[nw2 + (j >> 5)] >> (j & 31)) & 1u) continue;
-        const int s = (int)((w[j >> 4] >> ((j & 15) * 2)) & 3u);
-        const int k = rev ? len - 1 - j : j;
+        int s, k;
+        if (!fig_rs_base(w, len, rev, j, s, k)) continue;
         const int c = (int)S[j];
         lr = lr + (c > 3 ? FIG_P_LQ : c == s ? lm[k] : le[k] + lt[(c & 3) * 4 + s]);
     }
@@ -70,18 +61,6 @@ struct FigPlaceArgs {
     int32_t *off_other, *n_valid;
 };
 
-typedef const int32_t __attribute__((address_space(1))) *fig_p_gi32p;
-typedef const int64_t __attribute__((address_space(1))) *fig_p_gi64p;
-typedef const uint8_t __attribute__((address_space(1))) *fig_p_gu8p;
-typedef const char __attribute__((address_space(1))) *fig_p_gcp;
-typedef const uint32_t __attribute__((address_space(1))) *fig_p_gu32p;
-typedef const double __attribute__((address_space(1))) *fig_p_gcdp;
-typedef double __attribute__((address_space(1))) *fig_p_gdp;
-typedef int32_t __attribute__((address_space(1))) *fig_p_gip;
-typedef const uint32_t __attribute__((address_space(3))) *fig_p_lu32p;
-typedef const uint8_t __attribute__((address_space(3))) *fig_p_lu8p;
-typedef const double __attribute__((address_space(3))) *fig_p_ldp;
-
 __device__ inline double fig_p_wave_max(double v) {
     for (int m = 32; m >= 1; m >>= 1) { const double u = __shfl_xor(v, m, 64); v = u > v ? u : v; }
     return v;
@@ -99,53 +78,42 @@ __device__ inline double fig_p_wave_sum(double v) {
 // by shuffles and a ballot, across tiles in the wave's own LDS slot, across the four waves by one thread per read.  Pass 2 scores
 // again and sums 10^(Lr - M).  No atomics.
 __global__ void __launch_bounds__(FIG_P_NT) fig_placement_kernel(FigPlaceArgs A) {
-    __shared__ double s_tab[2 * FIG_P_MAXL + 16];
-    __shared__ int4 s_hdr[FIG_P_CHUNK];                          // {drawn offset, length (0 = not scored), reversed, left anchor}
-    __shared__ long long s_isz0[FIG_P_CHUNK];                    // insert size at o = 0
-    __shared__ uint32_t s_w[FIG_P_CHUNK][FIG_P_WORDS];
+    __shared__ double s_tab[FIG_RS_TAB];
+    __shared__ int4 s_hdr[FIG_RS_CHUNK];                         // {drawn offset, length (0 = not scored), reversed, left anchor}
+    __shared__ long long s_isz0[FIG_RS_CHUNK];                   // insert size at o = 0
+    __shared__ uint32_t s_w[FIG_RS_CHUNK][FIG_RS_WORDS];
     __shared__ uint8_t s_S[(FIG_P_WIN + 15) & ~15];
-    __shared__ double s_pmax[FIG_P_NT / 64][FIG_P_CHUNK], s_psum[FIG_P_NT / 64][FIG_P_CHUNK], s_drawn[FIG_P_CHUNK], s_M[FIG_P_CHUNK];
-    __shared__ int32_t s_poff[FIG_P_NT / 64][FIG_P_CHUNK], s_pcnt[FIG_P_NT / 64][FIG_P_CHUNK];
+    __shared__ double s_pmax[FIG_P_NT / 64][FIG_RS_CHUNK], s_psum[FIG_P_NT / 64][FIG_RS_CHUNK], s_drawn[FIG_RS_CHUNK], s_M[FIG_RS_CHUNK];
+    __shared__ int32_t s_poff[FIG_P_NT / 64][FIG_RS_CHUNK], s_pcnt[FIG_P_NT / 64][FIG_RS_CHUNK];
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int g = ((fig_p_gi32p)A.items)[2 * blockIdx.x], c0 = ((fig_p_gi32p)A.items)[2 * blockIdx.x + 1];
-    const FigDevGap __attribute__((address_space(1))) *gp = (const FigDevGap __attribute__((address_space(1))) *)A.gaps + g;
-    const int n = ((fig_p_gi32p)A.ncol)[g];
-    const int nc = min(FIG_P_CHUNK, gp->nU - c0);
+    const int g = ((fig_rs_gi32p)A.items)[2 * blockIdx.x], c0 = ((fig_rs_gi32p)A.items)[2 * blockIdx.x + 1];
+    fig_rs_ggapp gp = (fig_rs_ggapp)A.gaps + g;
+    const int n = ((fig_rs_gi32p)A.ncol)[g];
+    const int nc = min(FIG_RS_CHUNK, gp->nU - c0);
     const long long rbase = gp->uBase + c0;
     const long long gap_start = gp->gapStart;
     const int G0 = gp->G0;
     const int L = A.L, Tmin = A.Tmin, Tmax = A.Tmax, max_insert = A.max_insert;
-    fig_p_gu8p fl = (fig_p_gu8p)A.flank + gp->flankOff;
-    fig_p_gcp str = (fig_p_gcp)A.str + ((fig_p_gi64p)A.str_off)[g];
-    fig_p_gcdp tabs = (fig_p_gcdp)A.tabs, li = (fig_p_gcdp)A.li;
-    for (int i = tid; i < 2 * L + 16; i += FIG_P_NT) s_tab[i < 2 * L ? i : 2 * FIG_P_MAXL + (i - 2 * L)] = tabs[i];
-    fig_p_ldp lm = (fig_p_ldp)&s_tab[0], le = (fig_p_ldp)&s_tab[L], lt = (fig_p_ldp)&s_tab[2 * FIG_P_MAXL];
+    fig_rs_gu8p fl = (fig_rs_gu8p)A.flank + gp->flankOff;
+    fig_rs_gcp str = (fig_rs_gcp)A.str + ((fig_rs_gi64p)A.str_off)[g];
+    fig_rs_gcdp li = (fig_rs_gcdp)A.li;
+    fig_rs_stage_tables(s_tab, A.tabs, L, tid, FIG_P_NT);
+    fig_rs_ldp lm = (fig_rs_ldp)&s_tab[0], le = (fig_rs_ldp)&s_tab[L], lt = (fig_rs_ldp)&s_tab[2 * FIG_RS_MAXL];
     const double ninf = -__builtin_inf();
-    {   // stage the chunk: four lanes per read, five words each
-        fig_p_gi32p rlen = (fig_p_gi32p)A.u_len, raux = (fig_p_gi32p)A.u_aux, rpos = (fig_p_gi32p)A.u_pos, dpos = (fig_p_gi32p)A.draw_pos;
-        fig_p_gi64p rwoff = (fig_p_gi64p)A.u_woff;
-        fig_p_gu32p packed = (fig_p_gu32p)A.packed;
-        const int r = tid >> 2, q = tid & 3;
-        if (r < nc) {
-            const int o = dpos[rbase + r];
-            int len = rlen[rbase + r];
-            len = min(max(len, 0), L);                                     // (the packer admits no read longer than the model's L <= 200)
-            const int nw = ((len + 15) >> 4) + ((len + 31) >> 5);
-            const long long wo = rwoff[rbase + r];
-            for (int w = q; w < nw; w += 4) s_w[r][w] = packed[wo + w];
-            if (q == 0) {
-                const long long pos = rpos[rbase + r];
-                s_hdr[r] = make_int4(o, o == INT32_MIN ? 0 : len, raux[rbase + r] & 1, pos < gap_start ? 1 : 0);
-                s_isz0[r] = fig_placement_isz(pos, gap_start, G0, n, len, 0);
-            }
+    {   // stage the chunk
+        int r, o, len;
+        if (fig_rs_stage_reads(s_w, tid, nc, L, A.u_len, A.u_woff, A.packed, A.draw_pos, rbase, rbase, r, o, len)) {
+            const long long pos = ((fig_rs_gi32p)A.u_pos)[rbase + r];
+            s_hdr[r] = make_int4(o, o == INT32_MIN ? 0 : len, ((fig_rs_gi32p)A.u_aux)[rbase + r] & 1, pos < gap_start ? 1 : 0);
+            s_isz0[r] = fig_placement_isz(pos, gap_start, G0, n, len, 0);
         }
-        if (tid < FIG_P_CHUNK) { s_drawn[tid] = ninf; s_M[tid] = ninf; }
-        for (int i = tid; i < (FIG_P_NT / 64) * FIG_P_CHUNK; i += FIG_P_NT) {
+        if (tid < FIG_RS_CHUNK) { s_drawn[tid] = ninf; s_M[tid] = ninf; }
+        for (int i = tid; i < (FIG_P_NT / 64) * FIG_RS_CHUNK; i += FIG_P_NT) {
             (&s_pmax[0][0])[i] = ninf; (&s_psum[0][0])[i] = 0.0; (&s_poff[0][0])[i] = INT32_MAX; (&s_pcnt[0][0])[i] = 0;
         }
     }
     __syncthreads();
-    const int o_first = -(FIG_P_MAXL - 1);
+    const int o_first = -(FIG_RS_MAXL - 1);
     for (int pass = 0; pass < 2; pass++) {
         for (int x0 = o_first; x0 < n; x0 += FIG_P_NT) {
             for (int i = tid; i < FIG_P_WIN; i += FIG_P_NT) s_S[i] = (uint8_t)fig_placement_column(x0 + i, n, fl, str);
@@ -159,7 +127,7 @@ __global__ void __launch_bounds__(FIG_P_NT) fig_placement_kernel(FigPlaceArgs A)
                 const long long isz = h.w ? s_isz0[r] + o : s_isz0[r] - o;
                 const bool valid = o >= -(len - 1) && o <= n - 1 && fig_placement_valid(isz, Tmin, Tmax, max_insert);
                 double v = ninf;
-                if (valid) v = fig_placement_score(li[isz], (fig_p_lu8p)&s_S[tid], len, h.z, (fig_p_lu32p)&s_w[r][0], lm, le, lt);
+                if (valid) v = fig_placement_score(li[isz], (fig_rs_lu8p)&s_S[tid], len, h.z, (fig_rs_lu32p)&s_w[r][0], lm, le, lt);
                 const bool other = valid && o != h.x;
                 if (pass == 0) {
                     if (valid && o == h.x) s_drawn[r] = v;
@@ -194,12 +162,12 @@ __global__ void __launch_bounds__(FIG_P_NT) fig_placement_kernel(FigPlaceArgs A)
                 }
                 const double d = s_drawn[tid];
                 s_M[tid] = d > m ? d : m;
-                ((fig_p_gdp)A.ll_drawn)[ri] = d; ((fig_p_gdp)A.ll_other)[ri] = m;
-                ((fig_p_gip)A.off_other)[ri] = off == INT32_MAX ? INT32_MIN : off; ((fig_p_gip)A.n_valid)[ri] = cnt;
+                ((fig_rs_gdp)A.ll_drawn)[ri] = d; ((fig_rs_gdp)A.ll_other)[ri] = m;
+                ((fig_rs_gip)A.off_other)[ri] = off == INT32_MAX ? INT32_MIN : off; ((fig_rs_gip)A.n_valid)[ri] = cnt;
             } else {
                 double s = s_psum[0][tid];
                 for (int w = 1; w < FIG_P_NT / 64; w++) s = s + s_psum[w][tid];
-                ((fig_p_gdp)A.sum_other)[ri] = s;
+                ((fig_rs_gdp)A.sum_other)[ri] = s;
             }
         }
         __syncthreads();

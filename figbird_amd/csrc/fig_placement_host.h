@@ -1,6 +1,6 @@
 // fig_placement_host.h -- the device-free half of the placement confidence (fig_batch_placement, include/figbird_hip.h;
 // DESIGN.md §5d): the log10 table of the insert-size distribution, the insert size of a placement and whether it is valid, which
-// gaps are scored at all, the Phred of a read, and the bounds check of the drawn offsets.  Pure C++ (no HIP, no engine headers):
+// gaps are scored at all, and the Phred of a read (the drawn offsets are bounded as the quality's are, fig_quality_host.h).  Pure C++ (no HIP, no engine headers):
 // compiled into libfighip.so (fig_abi.hip, where the kernel of fig_placement.h calls the two marked functions on the device too)
 // and into libfighost.so / figfill (host/fig_host.cpp), so that the library, the writers and the tests share one statement of
 // each rule.
@@ -17,8 +17,6 @@
 #else
 #define FIG_P_HD
 #endif
-
-#define FIG_PLACE_MAX_OFFSET FIG_QUAL_MAX_OFFSET      // a drawn offset o with |o| >= this is FIG_EINVAL, as in fig_batch_quality
 
 // li[s] = log10(insertLengthDistSmoothed[s]); log10(0) = -inf is kept
 static inline void fig_placement_li(int32_t max_insert, const double *insd, double *li) {
@@ -53,9 +51,5 @@ static inline uint8_t fig_placement_phred(double ll_drawn, double ll_other, doub
     const double q = floor(-10 * log10(perr) + 0.5);
     return (uint8_t)(q < 0 ? 0 : q > FIG_PLACE_MAX_PQ ? FIG_PLACE_MAX_PQ : q);
 }
-
-// Drawn offsets of one gap's `n_reads` unmapped reads: INT32_MIN = not drawn, anything else inside +-FIG_PLACE_MAX_OFFSET.
-// Returns the number of drawn reads, or -1.
-static inline int64_t fig_placement_check_offsets(const int32_t *draw_pos, int64_t n_reads) { return fig_quality_check_placements(draw_pos, n_reads); }
 
 #endif

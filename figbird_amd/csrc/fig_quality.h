@@ -10,19 +10,11 @@
 #ifndef FIG_QUALITY_H
 #define FIG_QUALITY_H
 #include <stdint.h>
+#include "fig_readstage.h"
 
-#ifdef __HIPCC__
-#include <hip/hip_runtime.h>
-#include "fig_types.h"
-#define FIG_Q_HD __host__ __device__
-#else
-#define FIG_Q_HD
-#endif
-
-#define FIG_Q_NT 256                 // threads of a workgroup = columns of a column block
-#define FIG_Q_CHUNK 64               // reads staged in LDS at a time
-#define FIG_Q_WORDS 20               // dwords of a staged read: ceil(200/16) 2-bit words + ceil(200/32) N-mask words (pack_read, fig_pack.h)
-#define FIG_Q_MAXL 200               // FIG_MAX_READLEN
+#define FIG_Q_HD FIG_RS_HD
+#define FIG_Q_MAXL FIG_RS_MAXL       // (the bound tests/quality_column_main.cpp puts on its case file)
+#define FIG_Q_NT (4 * FIG_RS_CHUNK)  // threads of a workgroup = columns of a column block
 
 // The read index of base j is len-1-j for an unmapped read whose mate was reverse-complemented, j for every other read;
 // `aux` is FigDevReads::aux of the read (unmapped: bit 0 = isReverse; partial: the match column, which says nothing here).
@@ -35,10 +27,8 @@ template <typename WP, typename DP>
 FIG_Q_HD inline void fig_quality_add_read(double &a0, double &a1, double &a2, double &a3, int x, int o, int len, int rev, WP w, DP lm, DP le, DP lt) {
     const int j = x - o;
     if ((unsigned)j >= (unsigned)len) return;
-    const int nw2 = (len + 15) >> 4;
-    if ((w[nw2 + (j >> 5)] >> (j & 31)) & 1u) return;
-    const int s = (int)((w[j >> 4] >> ((j & 15) * 2)) & 3u);
-    const int k = rev ? len - 1 - j : j;
+    int s, k;
+    if (!fig_rs_base(w, len, rev, j, s, k)) return;
     const double m = lm[k], e = le[k];
     a0 = a0 + (s == 0 ? m : e + lt[0 + s]);
     a1 = a1 + (s == 1 ? m : e + lt[4 + s]);
@@ -64,62 +54,42 @@ struct FigQualArgs {
     double *loglik;                  // [(str_off[g] + x) * 4 + b]
 };
 
-typedef const int32_t __attribute__((address_space(1))) *fig_q_gi32p;
-typedef const int64_t __attribute__((address_space(1))) *fig_q_gi64p;
-typedef const uint8_t __attribute__((address_space(1))) *fig_q_gu8p;
-typedef const uint32_t __attribute__((address_space(1))) *fig_q_gu32p;
-typedef const double __attribute__((address_space(1))) *fig_q_gcdp;
-typedef double __attribute__((address_space(1))) *fig_q_gdp;
-typedef const uint32_t __attribute__((address_space(3))) *fig_q_lu32p;
-typedef const double __attribute__((address_space(3))) *fig_q_ldp;
-
 // One workgroup per gap that is on.  A lane owns column x = tid + 256 * i; per column block the gap's reads pass through LDS in
 // chunks of 64 (offset, length, reverse bit, 2-bit and N-mask words) and every lane walks the staged reads in order, adding into
 // four register accumulators.  No atomics: the order of the additions is part of the definition.
 __global__ void __launch_bounds__(FIG_Q_NT) fig_quality_kernel(FigQualArgs A) {
-    __shared__ double s_tab[2 * FIG_Q_MAXL + 16];
-    __shared__ int4 s_hdr[FIG_Q_CHUNK];                          // {offset, length (0 = takes no part), reversed, -}
-    __shared__ uint32_t s_w[FIG_Q_CHUNK][FIG_Q_WORDS];
+    __shared__ double s_tab[FIG_RS_TAB];
+    __shared__ int4 s_hdr[FIG_RS_CHUNK];                         // {offset, length (0 = takes no part), reversed, -}
+    __shared__ uint32_t s_w[FIG_RS_CHUNK][FIG_RS_WORDS];
     const int tid = (int)threadIdx.x;
-    const int g = ((fig_q_gi32p)A.list)[blockIdx.x];
-    const FigDevGap __attribute__((address_space(1))) *gp = (const FigDevGap __attribute__((address_space(1))) *)A.gaps + g;
-    const int part = ((fig_q_gu8p)A.partial)[g];
-    const int n = ((fig_q_gi32p)A.ncol)[g];
+    const int g = ((fig_rs_gi32p)A.list)[blockIdx.x];
+    fig_rs_ggapp gp = (fig_rs_ggapp)A.gaps + g;
+    const int part = ((fig_rs_gu8p)A.partial)[g];
+    const int n = ((fig_rs_gi32p)A.ncol)[g];
     const int nreads = part ? gp->nP : gp->nU;
     const long long rbase = part ? gp->pBase : gp->uBase;        // into the mode's FigDevReads arrays
     const long long dbase = part ? A.n_ureads + rbase : rbase;   // into the draw planes
-    const long long so = ((fig_q_gi64p)A.str_off)[g];
+    const long long so = ((fig_rs_gi64p)A.str_off)[g];
     const int L = A.L;
-    fig_q_gcdp tabs = (fig_q_gcdp)A.tabs;
-    for (int i = tid; i < 2 * L + 16; i += FIG_Q_NT) s_tab[i < 2 * L ? i : 2 * FIG_Q_MAXL + (i - 2 * L)] = tabs[i];
-    fig_q_ldp lm = (fig_q_ldp)&s_tab[0], le = (fig_q_ldp)&s_tab[L], lt = (fig_q_ldp)&s_tab[2 * FIG_Q_MAXL];
-    fig_q_gi32p rlen = (fig_q_gi32p)(part ? A.p_len : A.u_len);
-    fig_q_gi64p rwoff = (fig_q_gi64p)(part ? A.p_woff : A.u_woff);
-    fig_q_gi32p raux = (fig_q_gi32p)A.u_aux, dpos = (fig_q_gi32p)A.draw_pos;
-    fig_q_gu32p packed = (fig_q_gu32p)A.packed;
-    fig_q_gdp out = (fig_q_gdp)A.loglik;
+    fig_rs_stage_tables(s_tab, A.tabs, L, tid, FIG_Q_NT);
+    fig_rs_ldp lm = (fig_rs_ldp)&s_tab[0], le = (fig_rs_ldp)&s_tab[L], lt = (fig_rs_ldp)&s_tab[2 * FIG_RS_MAXL];
+    const int32_t *rlen = part ? A.p_len : A.u_len;
+    const int64_t *rwoff = part ? A.p_woff : A.u_woff;
+    fig_rs_gi32p raux = (fig_rs_gi32p)A.u_aux;
+    fig_rs_gdp out = (fig_rs_gdp)A.loglik;
     for (int xb = 0; xb < n; xb += FIG_Q_NT) {
         const int x = xb + tid;
         double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        for (int c0 = 0; c0 < nreads; c0 += FIG_Q_CHUNK) {
-            const int nc = min(FIG_Q_CHUNK, nreads - c0);
-            {   // stage: four lanes per read, five words each
-                const int r = tid >> 2, q = tid & 3;
-                if (r < nc) {
-                    const int o = dpos[dbase + c0 + r];
-                    int len = rlen[rbase + c0 + r];
-                    len = min(max(len, 0), L);                             // (the packer admits no read longer than the model's L <= 200)
-                    const int nw = ((len + 15) >> 4) + ((len + 31) >> 5);
-                    const long long wo = rwoff[rbase + c0 + r];
-                    for (int w = q; w < nw; w += 4) s_w[r][w] = packed[wo + w];
-                    if (q == 0) s_hdr[r] = make_int4(o == INT32_MIN ? 0 : o, o == INT32_MIN ? 0 : len, fig_quality_reversed(part, part ? 0 : raux[rbase + c0 + r]), 0);
-                }
-            }
+        for (int c0 = 0; c0 < nreads; c0 += FIG_RS_CHUNK) {
+            const int nc = min(FIG_RS_CHUNK, nreads - c0);
+            int r, o, len;
+            if (fig_rs_stage_reads(s_w, tid, nc, L, rlen, rwoff, A.packed, A.draw_pos, rbase + c0, dbase + c0, r, o, len))
+                s_hdr[r] = make_int4(o == INT32_MIN ? 0 : o, o == INT32_MIN ? 0 : len, fig_quality_reversed(part, part ? 0 : raux[rbase + c0 + r]), 0);
             __syncthreads();
             if (x < n) {
                 for (int r = 0; r < nc; r++) {
                     const int4 h = s_hdr[r];
-                    fig_quality_add_read(a0, a1, a2, a3, x, h.x, h.y, h.z, (fig_q_lu32p)&s_w[r][0], lm, le, lt);
+                    fig_quality_add_read(a0, a1, a2, a3, x, h.x, h.y, h.z, (fig_rs_lu32p)&s_w[r][0], lm, le, lt);
                 }
             }
             __syncthreads();

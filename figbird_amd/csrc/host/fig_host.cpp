@@ -717,24 +717,31 @@ void Batch::view(fig_gap_batch &b, const Scaffold &sc) const {
 }
 
 // ------------------------------------------------------------------ outputs
-bool write_gapout(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
-    FILE *f = fopen((a.tmp + "gapout.txt").c_str(), "w");
-    if (!f) { err = "can't write gapout.txt"; return false; }
+// <tmp>/<name>, one line per gap: the head `g contig start G0` and a tab, then whatever tail(f, g) prints, the newline included
+template <typename Tail>
+static bool write_per_gap(const RunArgs &a, const Batch &b, const char *name, std::string &err, Tail tail) {
+    FILE *f = fopen((a.tmp + name).c_str(), "w");
+    if (!f) { err = std::string("can't write ") + name; return false; }
     for (size_t g = 0; g < b.gap_contig.size(); g++) {
-        int n = r.filled_len[g];
-        fprintf(f, "%d\t%d\t%ld\t%d\t%d\t", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g], n);
-        if (n > 0) fwrite(r.str.data() + r.str_off[g], 1, (size_t)n, f);
-        fputc('\n', f);
+        fprintf(f, "%d\t%d\t%ld\t%d\t", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g]);
+        tail(f, g);
     }
     fclose(f);
     return true;
 }
 
+bool write_gapout(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+    return write_per_gap(a, b, "gapout.txt", err, [&](FILE *f, size_t g) {
+        const int n = r.filled_len[g];
+        fprintf(f, "%d\t", n);
+        if (n > 0) fwrite(r.str.data() + r.str_off[g], 1, (size_t)n, f);
+        fputc('\n', f);
+    });
+}
+
 bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
-    FILE *f = fopen((a.tmp + "gapsupport.txt").c_str(), "w");
-    if (!f) { err = "can't write gapsupport.txt"; return false; }
     std::string S, D;
-    for (size_t g = 0; g < b.gap_contig.size(); g++) {
+    return write_per_gap(a, b, "gapsupport.txt", err, [&](FILE *f, size_t g) {
         const int n = r.filled_len[g] > 0 ? r.filled_len[g] : 0;
         S.clear(); D.clear();
         for (int x = 0; x < n; x++) {
@@ -745,38 +752,28 @@ bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::stri
             S += std::to_string(k >= 0 ? c[k] : 0);
             D += std::to_string((long long)c[0] + c[1] + c[2] + c[3] + c[4]);
         }
-        fprintf(f, "%d\t%d\t%ld\t%d\t%d\t%d\t%s\t%s\n", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g], n, r.sup_origin[g], S.c_str(), D.c_str());
-    }
-    fclose(f);
-    return true;
+        fprintf(f, "%d\t%d\t%s\t%s\n", n, r.sup_origin[g], S.c_str(), D.c_str());
+    });
 }
 
 bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
-    FILE *f = fopen((a.tmp + "gapquality.txt").c_str(), "w");
-    if (!f) { err = "can't write gapquality.txt"; return false; }
     std::string Q;
-    for (size_t g = 0; g < b.gap_contig.size(); g++) {
+    return write_per_gap(a, b, "gapquality.txt", err, [&](FILE *f, size_t g) {
         const int n = r.filled_len[g];
         Q.clear();
         for (int x = 0; x < n; x++) Q += (char)(33 + r.qual_phred[(size_t)r.str_off[g] + x]);
-        fprintf(f, "%d\t%d\t%ld\t%d\t%d\t%d\t%s\n", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g], n, (int)r.qual_state[g], Q.c_str());
-    }
-    fclose(f);
-    return true;
+        fprintf(f, "%d\t%d\t%s\n", n, (int)r.qual_state[g], Q.c_str());
+    });
 }
 
 bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
-    FILE *f = fopen((a.tmp + "gapplacement.txt").c_str(), "w");
-    if (!f) { err = "can't write gapplacement.txt"; return false; }
     std::string Q;
-    for (size_t g = 0; g < b.gap_contig.size(); g++) {
+    return write_per_gap(a, b, "gapplacement.txt", err, [&](FILE *f, size_t g) {
         const int64_t r0 = g < b.u_read_off.size() ? b.u_read_off[g] : 0, r1 = g + 1 < b.u_read_off.size() ? b.u_read_off[g + 1] : r0;
         Q.clear();
         for (int64_t k = r0; k < r1; k++) { const uint8_t pq = r.place_pq[(size_t)k]; Q += pq == FIG_PLACE_NONE ? '~' : (char)(33 + pq); }
-        fprintf(f, "%d\t%d\t%ld\t%d\t%d\t%d\t%ld\t%s\n", (int)g, b.gap_contig[g], (long)b.gap_start[g], b.gap_len[g], r.filled_len[g], (int)r.place_state[g], (long)(r1 - r0), Q.c_str());
-    }
-    fclose(f);
-    return true;
+        fprintf(f, "%d\t%d\t%ld\t%s\n", r.filled_len[g], (int)r.place_state[g], (long)(r1 - r0), Q.c_str());
+    });
 }
 
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
@@ -1062,20 +1059,28 @@ extern "C" int fighost_run_write(void *h, const int32_t *filled_len, const int32
     return 0;
 }
 
+// What the three side writers below are handed alike: the string lengths of the WHOLE gap set and, for a plane indexed like the
+// strings, their offsets
+static fighost::Results side_results(const Run *r, const int32_t *filled_len, const int64_t *str_off) {
+    const size_t ng = r->B.gap_contig.size();
+    fighost::Results R;
+    R.filled_len.assign(filled_len, filled_len + ng);
+    if (str_off) R.str_off.assign(str_off, str_off + ng + 1);
+    return R;
+}
+static int written(bool ok, const std::string &e, char *err, int errcap) { if (!ok) set_err(err, errcap, e); return ok ? 0 : -1; }
+
 // gapsupport.txt of the WHOLE gap set (FIGFILL_SUPPORT=1): sup_counts [str_off[n_gaps]*5] indexed like str, sup_origin [n_gaps]
 extern "C" int fighost_run_write_support(void *h, const int32_t *filled_len, const int64_t *str_off, const char *str,
                                          const int32_t *sup_counts, const int32_t *sup_origin, char *err, int errcap) {
     Run *r = (Run *)h;
     const size_t ng = r->B.gap_contig.size();
-    fighost::Results R;
-    R.filled_len.assign(filled_len, filled_len + ng);
-    R.str_off.assign(str_off, str_off + ng + 1);
+    fighost::Results R = side_results(r, filled_len, str_off);
     R.str.assign(str, str + (size_t)str_off[ng]);
     R.sup_counts.assign(sup_counts, sup_counts + (size_t)str_off[ng] * 5);
     R.sup_origin.assign(sup_origin, sup_origin + ng);
     std::string e;
-    if (!fighost::write_support(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
-    return 0;
+    return written(fighost::write_support(r->a, r->B, R, e), e, err, errcap);
 }
 
 // ------------------------------------------------------------------ per-base quality (fig_quality_host.h)
@@ -1103,14 +1108,11 @@ extern "C" int fighost_run_write_quality(void *h, const int32_t *filled_len, con
                                          char *err, int errcap) {
     Run *r = (Run *)h;
     const size_t ng = r->B.gap_contig.size();
-    fighost::Results R;
-    R.filled_len.assign(filled_len, filled_len + ng);
-    R.str_off.assign(str_off, str_off + ng + 1);
+    fighost::Results R = side_results(r, filled_len, str_off);
     R.qual_phred.assign(phred, phred + (size_t)str_off[ng]);
     R.qual_state.assign(state, state + ng);
     std::string e;
-    if (!fighost::write_quality(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
-    return 0;
+    return written(fighost::write_quality(r->a, r->B, R, e), e, err, errcap);
 }
 
 // ------------------------------------------------------------------ placement confidence (fig_placement_host.h)
@@ -1140,12 +1142,9 @@ extern "C" int fighost_placement_gaps_on(int unmapped_model, int64_t ng, const i
 // gapplacement.txt of the WHOLE gap set (FIGFILL_PLACEMENT=1): pq [unmapped reads] indexed like draw_pos, state [n_gaps]
 extern "C" int fighost_run_write_placement(void *h, const int32_t *filled_len, const uint8_t *pq, const uint8_t *state, char *err, int errcap) {
     Run *r = (Run *)h;
-    const size_t ng = r->B.gap_contig.size(), nu = r->B.u_anchor_pos.size();
-    fighost::Results R;
-    R.filled_len.assign(filled_len, filled_len + ng);
-    R.place_pq.assign(pq, pq + nu);
-    R.place_state.assign(state, state + ng);
+    fighost::Results R = side_results(r, filled_len, nullptr);
+    R.place_pq.assign(pq, pq + r->B.u_anchor_pos.size());
+    R.place_state.assign(state, state + r->B.gap_contig.size());
     std::string e;
-    if (!fighost::write_placement(r->a, r->B, R, e)) { set_err(err, errcap, e); return -1; }
-    return 0;
+    return written(fighost::write_placement(r->a, r->B, R, e), e, err, errcap);
 }

@@ -19,31 +19,32 @@
 
 using namespace fighost;
 
-// fig_fill_resident_ex is the one call of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests
-// implements the calls it was written against): bound weakly, and asking for the support plane without it is an error.
+// Three calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
+// written against): bound weakly, and asking for what they compute without them is an error before anything is filled or written.
 extern "C" int fig_fill_resident_ex(fig_ctx *, fig_gap_results *, const fig_gap_support *) __attribute__((weak));
-
-// fig_batch_quality likewise: FIGFILL_QUALITY=1 on a library without it is an error before anything is filled or written.
 extern "C" int fig_batch_quality(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_quality *) __attribute__((weak));
-
-// FIGFILL_SUPPORT=1: also ask for the per-base read support and write <tmp>/gapsupport.txt
-static bool want_support() { const char *s = getenv("FIGFILL_SUPPORT"); return s && atoi(s) == 1; }
-
-// FIGFILL_QUALITY=1: the fill with the support call (for the origins), then fig_batch_quality, and <tmp>/gapquality.txt
-static bool want_quality() { const char *s = getenv("FIGFILL_QUALITY"); return s && atoi(s) == 1; }
-
-// fig_batch_placement likewise: FIGFILL_PLACEMENT=1 or FIGFILL_QUALITY_MINPQ on a library without it is an error before anything
-// is filled or written.
 extern "C" int fig_batch_placement(fig_ctx *, const fig_gap_results *, const int32_t *, fig_read_placement *) __attribute__((weak));
 
-// FIGFILL_PLACEMENT=1: the fill with the support call (for the origins), then fig_batch_placement, and <tmp>/gapplacement.txt
-static bool want_placement_file() { const char *s = getenv("FIGFILL_PLACEMENT"); return s && atoi(s) == 1; }
+// The optional outputs: read from the environment once, in main(), and passed down.
+//   FIGFILL_SUPPORT=1    also the per-base read support and <tmp>/gapsupport.txt
+//   FIGFILL_QUALITY=1    the fill with the support call (for the origins), then fig_batch_quality, and <tmp>/gapquality.txt
+//   FIGFILL_PLACEMENT=1  the fill with the support call, then fig_batch_placement, and <tmp>/gapplacement.txt
+//   FIGFILL_QUALITY_MINPQ=<k> (only together with FIGFILL_QUALITY=1): the quality leaves out scored reads with pq < k
+struct Wants {
+    bool support_file = false, quality = false, placement_file = false;
+    int min_pq = -1;                                                            // -1 = not set
+    bool placement() const { return placement_file || min_pq >= 0; }            // the call is needed for the file and for the filter
+    bool support() const { return support_file || quality || placement(); }
+};
 
-// FIGFILL_QUALITY_MINPQ=<k> (only together with FIGFILL_QUALITY=1): the quality leaves out scored reads with pq < k; -1 = not set
-static int quality_min_pq() { const char *s = getenv("FIGFILL_QUALITY_MINPQ"); return s && *s && want_quality() ? atoi(s) : -1; }
-
-// the placement call is needed for the file and for the filter
-static bool want_placement() { return want_placement_file() || quality_min_pq() >= 0; }
+static Wants wants_from_env() {
+    auto is1 = [](const char *name) { const char *s = getenv(name); return s && atoi(s) == 1; };
+    Wants w;
+    w.support_file = is1("FIGFILL_SUPPORT"); w.quality = is1("FIGFILL_QUALITY"); w.placement_file = is1("FIGFILL_PLACEMENT");
+    const char *s = getenv("FIGFILL_QUALITY_MINPQ");
+    w.min_pq = s && *s && w.quality ? atoi(s) : -1;
+    return w;
+}
 
 // the placement confidence of the fill `fr` just returned (the batch still resident): R.place_pq / R.place_state
 static int placement_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu) {
@@ -58,26 +59,50 @@ static int placement_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &
 }
 
 // the per-base quality of the fill `fr` just returned (the batch still resident): R.qual_phred / R.qual_state.  With
-// FIGFILL_QUALITY_MINPQ the call sees a copy of the draw plane in which the scored reads below the bound are not drawn.
-static int quality_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu) {
+// min_pq >= 0 the call sees a copy of the draw plane in which the scored reads below the bound are not drawn.
+static int quality_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu, int min_pq) {
     R.qual_phred.assign((size_t)std::max<int64_t>(fr->str_capacity, 1), 0); R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
     std::vector<double> ll((size_t)std::max<int64_t>(fr->str_off[ng], 1) * 4, 0.0);
     fig_gap_quality gq; gq.loglik = ll.data(); gq.phred = R.qual_phred.data(); gq.state = R.qual_state.data();
-    const int k = quality_min_pq();
-    if (k < 0) return fig_batch_quality(ctx, fr, R.sup_origin.data(), &gq);
+    if (min_pq < 0) return fig_batch_quality(ctx, fr, R.sup_origin.data(), &gq);
     std::vector<int32_t> kept(R.draw_pos);
-    for (int64_t r = 0; r < nu; r++) if (R.place_pq[(size_t)r] != FIG_PLACE_NONE && R.place_pq[(size_t)r] < k) kept[(size_t)r] = INT32_MIN;
+    for (int64_t r = 0; r < nu; r++) if (R.place_pq[(size_t)r] != FIG_PLACE_NONE && R.place_pq[(size_t)r] < min_pq) kept[(size_t)r] = INT32_MIN;
     fig_gap_results f2 = *fr; f2.draw_pos = kept.data();
     return fig_batch_quality(ctx, &f2, R.sup_origin.data(), &gq);
 }
 
-// the fill, with R.sup_counts / R.sup_origin sized and filled when `support`
-static int fill_resident(fig_ctx *ctx, fig_gap_results *fr, Results &R, int64_t ng, bool support) {
-    if (!support) return fig_fill_resident(ctx, fr);
-    if (!fig_fill_resident_ex) { fprintf(stderr, "figfill: FIGFILL_SUPPORT=1 needs fig_fill_resident_ex, which the library behind this build does not export\n"); return FIG_EUNSUP; }
-    R.sup_counts.assign((size_t)std::max<int64_t>(fr->str_capacity, 1) * 5, 0); R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
-    fig_gap_support fs; fs.counts = R.sup_counts.data(); fs.origin = R.sup_origin.data();
-    return fig_fill_resident_ex(ctx, fr, &fs);
+// The fill of the batch `fb` (nu unmapped + np partial reads) resident in ctx, as both the single-device path and a shard run it:
+// R is sized, `fr` -- zeroed by the caller, who may have set its dbg_* fields -- becomes the view of R the library fills, then
+// the fill (with R.sup_counts / R.sup_origin when `w` needs the support call) and the passes beside it that `w` asks for.
+// Returns 0, or the failing call's code with its name in `what`.
+static const char *const FILL_CALL = "fig_fill_resident";
+static int fill_batch(fig_ctx *ctx, const fig_model *fm, const fig_gap_batch *fb, int64_t nu, int64_t np, const Wants &w, Results &R, fig_gap_results &fr,
+                      fig_stats *st, const char *&what) {
+    const int64_t ng = fb->n_gaps, nr = nu + np, cap = fig_results_capacity(fm, fb);
+    R.filled_len.assign(ng, 0); R.gaptofill.assign(ng, 0); R.str_off.assign(ng + 1, 0); R.str.assign((size_t)std::max<int64_t>(cap, 1), 'N');
+    R.draw_pos.assign((size_t)std::max<int64_t>(nr, 1), INT32_MIN); R.draw_isz.assign((size_t)std::max<int64_t>(nr, 1), 0); R.draw_len.assign((size_t)std::max<int64_t>(ng * 2, 1), -1);
+    fr.filled_len = R.filled_len.data(); fr.gaptofill = R.gaptofill.data(); fr.str_off = R.str_off.data();
+    fr.str = &R.str[0]; fr.str_capacity = (int64_t)R.str.size();
+    fr.draw_pos = R.draw_pos.data(); fr.draw_isz = R.draw_isz.data(); fr.draw_len = R.draw_len.data();
+    what = FILL_CALL;
+    int rc;
+    if (!w.support()) rc = fig_fill_resident(ctx, &fr);
+    else if (!fig_fill_resident_ex) { fprintf(stderr, "figfill: FIGFILL_SUPPORT=1 needs fig_fill_resident_ex, which the library behind this build does not export\n"); rc = FIG_EUNSUP; }
+    else {
+        R.sup_counts.assign((size_t)std::max<int64_t>(fr.str_capacity, 1) * 5, 0); R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
+        fig_gap_support fs; fs.counts = R.sup_counts.data(); fs.origin = R.sup_origin.data();
+        rc = fig_fill_resident_ex(ctx, &fr, &fs);
+    }
+    fig_get_stats(ctx, st);
+    if (!rc && w.placement()) { what = "fig_batch_placement"; rc = placement_resident(ctx, &fr, R, ng, nu); }
+    if (!rc && w.quality) { what = "fig_batch_quality"; rc = quality_resident(ctx, &fr, R, ng, nu, w.min_pq); }
+    return rc;
+}
+
+// every file of a run
+static bool write_outputs(const RunArgs &a, const Scaffold &sc, const Batch &B, const Results &R, const Wants &w, std::string &err) {
+    return write_gapout(a, B, R, err) && write_draw(a, B, R, err) && write_gaploads(a, B, err) && write_scaffold(a, sc, B, R, err) &&
+           (!w.support_file || write_support(a, B, R, err)) && (!w.quality || write_quality(a, B, R, err)) && (!w.placement_file || write_placement(a, B, R, err));
 }
 
 static int fail(const std::string &m) { fprintf(stderr, "%s\n", m.c_str()); return 1; }
@@ -87,7 +112,7 @@ static int fail(const std::string &m) { fprintf(stderr, "%s\n", m.c_str()); retu
 // FillGaps.cpp:456-649), one host thread per GPU creates its own fig_ctx (contexts are independent, include/figbird_hip.h)
 // and fills its shard through fig_fill_gaps with no exchange on the data path; the shard results meet in host memory in
 // global gap / read order, so the writers below see exactly what a single-GPU run hands them.
-struct ShardRun { std::vector<int64_t> ids; Batch sub; Results R; fig_stats st; int rc = 0; std::string err; fig_ctx *ctx = nullptr; std::vector<uint8_t> reach, preset; };
+struct ShardRun { Wants w; std::vector<int64_t> ids; Batch sub; Results R; fig_stats st; int rc = 0; std::string err; fig_ctx *ctx = nullptr; std::vector<uint8_t> reach, preset; };
 
 static void shard_fail(ShardRun *S, int rc, const std::string &what) {
     S->rc = rc; S->err = what + ": " + fig_strerror(rc);
@@ -115,32 +140,21 @@ static void shard_fill(int device, const fig_model *fm, const Scaffold *sc, Shar
     if (ng == 0 || !S->ctx) return;
     int rc = fig_batch_set_ot_preset(S->ctx, S->preset.data());
     if (rc) return shard_fail(S, rc, "fig_batch_set_ot_preset");
-    Results &R = S->R;
-    const int64_t cap = fig_results_capacity(fm, &fb);
-    R.filled_len.assign(ng, 0); R.gaptofill.assign(ng, 0); R.str_off.assign(ng + 1, 0); R.str.assign((size_t)std::max<int64_t>(cap, 1), 'N');
-    const int64_t nr = (int64_t)S->sub.u_anchor_pos.size() + (int64_t)S->sub.p_pos.size();
-    R.draw_pos.assign((size_t)std::max<int64_t>(nr, 1), INT32_MIN); R.draw_isz.assign((size_t)std::max<int64_t>(nr, 1), 0); R.draw_len.assign((size_t)std::max<int64_t>(ng * 2, 1), -1);
     fig_gap_results fr; memset(&fr, 0, sizeof(fr));
-    fr.filled_len = R.filled_len.data(); fr.gaptofill = R.gaptofill.data(); fr.str_off = R.str_off.data();
-    fr.str = &R.str[0]; fr.str_capacity = (int64_t)R.str.size();
-    fr.draw_pos = R.draw_pos.data(); fr.draw_isz = R.draw_isz.data(); fr.draw_len = R.draw_len.data();
-    rc = fill_resident(S->ctx, &fr, R, ng, want_support() || want_quality() || want_placement());
-    fig_get_stats(S->ctx, &S->st);
-    if (rc) return shard_fail(S, rc, std::string("fig_fill_resident on device ") + std::to_string(device));
-    const int64_t snu = (int64_t)S->sub.u_anchor_pos.size();
-    if (want_placement() && (rc = placement_resident(S->ctx, &fr, R, ng, snu))) return shard_fail(S, rc, std::string("fig_batch_placement on device ") + std::to_string(device));
-    if (want_quality() && (rc = quality_resident(S->ctx, &fr, R, ng, snu))) return shard_fail(S, rc, std::string("fig_batch_quality on device ") + std::to_string(device));
+    const char *what;
+    rc = fill_batch(S->ctx, fm, &fb, (int64_t)S->sub.u_anchor_pos.size(), (int64_t)S->sub.p_pos.size(), S->w, S->R, fr, &S->st, what);
+    if (rc) return shard_fail(S, rc, std::string(what) + " on device " + std::to_string(device));
     fig_ctx_destroy(S->ctx); S->ctx = nullptr;
 }
 
 // Fill B over `devices`; on success R holds the whole gap set in global order.  Returns 0 or 1 (message in err).
-static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const Scaffold &sc, Batch &B, const fig_model &fm, Results &R,
+static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const Scaffold &sc, Batch &B, const fig_model &fm, const Wants &w, Results &R,
                       fig_stats &st, std::string &err) {
     const int world = (int)devices.size();
     const int64_t ng = (int64_t)B.gap_contig.size();
     std::vector<std::vector<int64_t>> shards = partition_lpt(estimate_cost(B, a, fm.max_read_length), world);
     std::vector<ShardRun> runs((size_t)world);
-    for (int r = 0; r < world; r++) { runs[r].ids = shards[r]; make_shard(B, shards[r], runs[r].sub); }
+    for (int r = 0; r < world; r++) { runs[r].w = w; runs[r].ids = shards[r]; make_shard(B, shards[r], runs[r].sub); }
     const bool serial = getenv("FIGFILL_SERIAL") != nullptr;   // test knob: one shard after the other (the CPU emulation library keeps global state)
     auto phase = [&](void (*fn)(int, const fig_model *, const Scaffold *, ShardRun *)) {
         if (serial) { for (int r = 0; r < world; r++) fn(devices[r], &fm, &sc, &runs[r]); return; }
@@ -171,7 +185,7 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         st.n_launches += runs[r].st.n_launches;
     }
     R.str.clear();
-    const bool support = want_support() || want_quality() || want_placement(), quality = want_quality(), placement = want_placement();
+    const bool support = w.support(), quality = w.quality, placement = w.placement();
     if (support) R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
     if (placement) { R.place_pq.assign((size_t)std::max<int64_t>(NU, 1), FIG_PLACE_NONE); R.place_state.assign((size_t)std::max<int64_t>(ng, 1), 0); }
     if (quality) R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
@@ -232,9 +246,10 @@ int main(int argc, char **argv) {
         }
         if (devices.empty()) return fail("figfill: FIGFILL_DEVICES must be a comma-separated list of GPU ordinals");
     }
-    if (want_placement() && !fig_batch_placement)
+    const Wants w = wants_from_env();
+    if (w.placement() && !fig_batch_placement)
         return fail("figfill: FIGFILL_PLACEMENT=1 and FIGFILL_QUALITY_MINPQ need fig_batch_placement, which the library behind this build does not export");
-    if (want_quality() && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
+    if (w.quality && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
     setenv("GPU_MAX_HW_QUEUES", "8", 0);                 // one hardware queue per scheduler lane; before any thread or HIP call (fig_abi.hip: fig_ctx_create)
     auto t0 = std::chrono::steady_clock::now();
 
@@ -271,14 +286,8 @@ int main(int argc, char **argv) {
     fig_gap_batch fb; B.view(fb, sc);
     if (devices.size() > 1) {
         Results R; fig_stats st;
-        if (fill_multi(devices, a, sc, B, fm, R, st, err)) return fail(err);
-        if (!write_gapout(a, B, R, err)) return fail(err);
-        if (!write_draw(a, B, R, err)) return fail(err);
-        if (!write_gaploads(a, B, err)) return fail(err);
-        if (!write_scaffold(a, sc, B, R, err)) return fail(err);
-        if (want_support() && !write_support(a, B, R, err)) return fail(err);
-        if (want_quality() && !write_quality(a, B, R, err)) return fail(err);
-        if (want_placement_file() && !write_placement(a, B, R, err)) return fail(err);
+        if (fill_multi(devices, a, sc, B, fm, w, R, st, err)) return fail(err);
+        if (!write_outputs(a, sc, B, R, w, err)) return fail(err);
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         printf("Time taken = %g seconds (%zu GPUs; slowest shard's device kernels %.3f ms, %lld placeReads calls)\n", secs, devices.size(), st.kernel_ms, (long long)st.place_calls);
         printf("======================================\n");
@@ -294,15 +303,8 @@ int main(int argc, char **argv) {
     if (rc) { fig_ctx_destroy(ctx); return fail(std::string("figfill: fig_ctx_set_model: ") + fig_strerror(rc)); }
 
     Results R;
-    int64_t ng = fb.n_gaps;
-    int64_t cap = fig_results_capacity(&fm, &fb);
-    R.filled_len.assign(ng, 0); R.gaptofill.assign(ng, 0); R.str_off.assign(ng + 1, 0); R.str.assign((size_t)std::max<int64_t>(cap, 1), 'N');
-    int64_t nr = (int64_t)B.u_anchor_pos.size() + (int64_t)B.p_pos.size();
-    R.draw_pos.assign((size_t)std::max<int64_t>(nr, 1), INT32_MIN); R.draw_isz.assign((size_t)std::max<int64_t>(nr, 1), 0); R.draw_len.assign((size_t)std::max<int64_t>(ng * 2, 1), -1);
+    const int64_t ng = fb.n_gaps;
     fig_gap_results fr; memset(&fr, 0, sizeof(fr));
-    fr.filled_len = R.filled_len.data(); fr.gaptofill = R.gaptofill.data(); fr.str_off = R.str_off.data();
-    fr.str = &R.str[0]; fr.str_capacity = (int64_t)R.str.size();
-    fr.draw_pos = R.draw_pos.data(); fr.draw_isz = R.draw_isz.data(); fr.draw_len = R.draw_len.data();
     // optional candidate trace for the parity tests (FIGFILL_TRACE=<file>)
     const char *trace = getenv("FIGFILL_TRACE");
     std::vector<int32_t> dn, di; std::vector<double> dl;
@@ -319,23 +321,13 @@ int main(int argc, char **argv) {
         rc = fig_batch_probe_reach(ctx, reach.data());
         if (!rc) { ot_presets_from_reach(B, reach.data()); rc = fig_batch_set_ot_preset(ctx, B.gap_ot_preset.data()); }
     }
-    if (!rc) rc = fill_resident(ctx, &fr, R, ng, want_support() || want_quality() || want_placement());
-    fig_stats st; memset(&st, 0, sizeof(st)); fig_get_stats(ctx, &st);
-    int qrc = 0, prc = 0;
-    if (!rc && want_placement()) prc = placement_resident(ctx, &fr, R, ng, (int64_t)B.u_anchor_pos.size());
-    if (!rc && !prc && want_quality()) qrc = quality_resident(ctx, &fr, R, ng, (int64_t)B.u_anchor_pos.size());
+    fig_stats st; memset(&st, 0, sizeof(st));
+    const char *what = FILL_CALL;
+    if (!rc) rc = fill_batch(ctx, &fm, &fb, (int64_t)B.u_anchor_pos.size(), (int64_t)B.p_pos.size(), w, R, fr, &st, what);
     fig_ctx_destroy(ctx);
-    if (rc) return fail(std::string("figfill: fill: ") + fig_strerror(rc));
-    if (prc) return fail(std::string("figfill: fig_batch_placement: ") + fig_strerror(prc));
-    if (qrc) return fail(std::string("figfill: fig_batch_quality: ") + fig_strerror(qrc));
+    if (rc) return fail(std::string("figfill: ") + (what == FILL_CALL ? "fill" : what) + ": " + fig_strerror(rc));
 
-    if (!write_gapout(a, B, R, err)) return fail(err);
-    if (!write_draw(a, B, R, err)) return fail(err);
-    if (!write_gaploads(a, B, err)) return fail(err);
-    if (!write_scaffold(a, sc, B, R, err)) return fail(err);
-    if (want_support() && !write_support(a, B, R, err)) return fail(err);
-    if (want_quality() && !write_quality(a, B, R, err)) return fail(err);
-    if (want_placement_file() && !write_placement(a, B, R, err)) return fail(err);
+    if (!write_outputs(a, sc, B, R, w, err)) return fail(err);
     if (trace) {
         FILE *f = fopen(trace, "w");
         if (f) {

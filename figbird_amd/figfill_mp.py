@@ -25,6 +25,26 @@ import numpy as np
 from . import api, dist as fdist
 
 
+def _env_int(name: str):
+    """an environment variable as figfill reads it with atoi: its leading integer, or None"""
+    m = re.match(r"\s*[+-]?\d+", os.environ.get(name, ""))
+    return int(m.group(0)) if m is not None else None
+
+
+# The optional planes of a shard's result, described once: the switch that turns the plane on, its name on rank 0, the shard's
+# array, what it is indexed by -- "byte": the shard's string bytes, back to back in its own gap order (any trailing shape: the
+# support has five counts per byte); "gap"; "uread": the shard's unmapped reads -- and the width and the fill of the global array.
+# They travel after the draw planes as int32 extras in this order, and rank 0 scatters them by walking the same list.
+PLANES = (
+    ("support", "sup", lambda r: r.support.reshape(-1), "byte", (5,), np.int32, 0),
+    ("support", "org", lambda r: r.support_origin, "gap", (), np.int32, 0),
+    ("quality", "phr", lambda r: r.quality[1], "byte", (), np.uint8, 0),
+    ("quality", "qst", lambda r: r.quality[2], "gap", (), np.uint8, 0),
+    ("placement", "ppq", lambda r: r.placement.pq, "uread", (), np.uint8, api.PLACE_NONE),
+    ("placement", "pst", lambda r: r.placement.state, "gap", (), np.uint8, 0),
+)
+
+
 def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) -> int:
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # one hardware queue per scheduler lane; before the HIP runtime starts (fig_ctx_create)
     import torch
@@ -33,18 +53,13 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0")) if device_index is None else device_index
     t0 = time.time()
-    # FIGFILL_SUPPORT=1: also gapsupport.txt, the per-base read support (fig_gap_support); read as figfill reads it, atoi(s) == 1
-    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_SUPPORT", ""))
-    support = m is not None and int(m.group(0)) == 1
-    # FIGFILL_QUALITY=1: also gapquality.txt, the per-base Phred (fig_gap_quality); the fill then runs with the support call
-    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_QUALITY", ""))
-    quality = m is not None and int(m.group(0)) == 1
-    # FIGFILL_PLACEMENT=1: also gapplacement.txt, the placement confidence per drawn unmapped read (fig_read_placement);
-    # FIGFILL_QUALITY_MINPQ=<k> (only with FIGFILL_QUALITY=1): the quality leaves out the scored reads with pq < k
-    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_PLACEMENT", ""))
-    placement = m is not None and int(m.group(0)) == 1
-    m = re.match(r"\s*[+-]?\d+", os.environ.get("FIGFILL_QUALITY_MINPQ", ""))
-    min_pq = int(m.group(0)) if (m is not None and quality) else None
+    # FIGFILL_SUPPORT=1: also gapsupport.txt, the per-base read support (fig_gap_support); FIGFILL_QUALITY=1: also gapquality.txt,
+    # the per-base Phred (fig_gap_quality); FIGFILL_PLACEMENT=1: also gapplacement.txt, the placement confidence per drawn unmapped
+    # read (fig_read_placement) -- any of them runs the fill with the support call; FIGFILL_QUALITY_MINPQ=<k> (only with
+    # FIGFILL_QUALITY=1): the quality leaves out the scored reads with pq < k
+    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement")}
+    support, quality, placement = on["support"], on["quality"], on["placement"]
+    min_pq = _env_int("FIGFILL_QUALITY_MINPQ") if quality else None
     if min_pq is not None and min_pq < 0:
         min_pq = None
     own_pg = False
@@ -126,13 +141,8 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
         if fdist.all_status_max(prc, dev) != 0:
             return 1
         dpos, disz, dlen = res.draw
-        # the support plane travels as two more extras: the shard's counts, five per string byte in shard order, and its origins
-        sup_x = [res.support.reshape(-1), res.support_origin] if support else []
-        # and so does the quality: the shard's Phred, one per string byte in shard order, and its states (widened to the extras' int32)
-        qual_x = [res.quality[1].astype(np.int32), res.quality[2].astype(np.int32)] if quality else []
-        # and the placement: the shard's pq, one per unmapped read in shard order, and its states
-        place_x = [res.placement.pq.astype(np.int32), res.placement.state.astype(np.int32)] if placement else []
-        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz] + sup_x + qual_x + place_x)
+        planes = [p for p in PLANES if on[p[0]]]
+        out = fdist.all_gather_packed(mine, res, n, device=dev, extras=[dlen, dpos, disz] + [p[2](res).astype(np.int32) for p in planes])
         wrc = 0
         try:
             fl, gt, ps, per_rank = out
@@ -142,35 +152,25 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 NU, NP = int(uo[-1]), int(po[-1])
                 g_pos = np.full(max(NU + NP, 1), np.iinfo(np.int32).min, dtype=np.int32); g_isz = np.zeros(max(NU + NP, 1), dtype=np.int32)
                 g_len = np.full(max(2 * n, 1), -1, dtype=np.int32)
-                g_sup = np.zeros((max(int(ps.off[-1]), 1), 5), dtype=np.int32); g_org = np.zeros(max(n, 1), dtype=np.int32)
-                g_phr = np.zeros(max(int(ps.off[-1]), 1), dtype=np.uint8); g_qst = np.zeros(max(n, 1), dtype=np.uint8)
-                g_ppq = np.full(max(NU, 1), api.PLACE_NONE, dtype=np.uint8); g_pst = np.zeros(max(n, 1), dtype=np.uint8)
+                rows = {"byte": max(int(ps.off[-1]), 1), "gap": max(n, 1), "uread": max(NU, 1)}
+                G = {name: np.full((rows[kind],) + width, fill, dtype=dt) for _, name, _, kind, width, dt, fill in PLANES}
                 for ids, r_len, r_pos, r_isz, *r_x in per_rank:
                     ids = np.asarray(ids, dtype=np.int64)
                     if len(ids) == 0:
                         continue
-                    r_sup, r_x = (r_x[:2], r_x[2:]) if support else ([], r_x)
-                    r_qual, r_place = (r_x[:2], r_x[2:]) if quality else ([], r_x)
-                    if support or quality:      # a shard's strings lie back to back in its own gap order; ps.off is the global layout
-                        ln = np.maximum(fl[ids], 0).astype(np.int64)
-                        src0 = np.cumsum(ln) - ln
-                        idx = np.repeat(ps.off[ids] - src0, ln) + np.arange(int(ln.sum()), dtype=np.int64)
-                    if support:
-                        g_sup[idx] = r_sup[0].reshape(-1, 5)[:int(ln.sum())]
-                        g_org[ids] = r_sup[1]
-                    if quality:
-                        g_phr[idx] = r_qual[0][:int(ln.sum())]
-                        g_qst[ids] = r_qual[1]
+                    # a shard's strings lie back to back in its own gap order; ps.off is the global layout
+                    ln = np.maximum(fl[ids], 0).astype(np.int64)
+                    src0 = np.cumsum(ln) - ln
+                    idx = np.repeat(ps.off[ids] - src0, ln) + np.arange(int(ln.sum()), dtype=np.int64)
                     g_len[2 * ids] = r_len[0::2]; g_len[2 * ids + 1] = r_len[1::2]
                     cu = nu[ids]; cp = npp[ids]
                     su_ = int(cu.sum())
                     src_u = np.arange(su_, dtype=np.int64)
                     dst_u = np.repeat(uo[ids] - (np.cumsum(cu) - cu), cu) + src_u
                     g_pos[dst_u] = r_pos[:su_]; g_isz[dst_u] = r_isz[:su_]
-                    if placement and unmapped:
-                        g_ppq[dst_u] = r_place[0][:su_]
-                    if placement:
-                        g_pst[ids] = r_place[1]
+                    dst = {"byte": idx, "gap": ids, "uread": dst_u if unmapped else dst_u[:0]}
+                    for (_, name, _, kind, width, _, _), arr in zip(planes, r_x):
+                        G[name][dst[kind]] = arr.reshape((-1,) + width)[:len(dst[kind])]
                     sp_ = int(cp.sum())
                     src_p = np.arange(sp_, dtype=np.int64)
                     dst_p = NU + np.repeat(po[ids] - (np.cumsum(cp) - cp), cp) + src_p
@@ -181,12 +181,12 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                                              api._p(g_pos, api.c_i32_p), api._p(g_isz, api.c_i32_p), api._p(g_len, api.c_i32_p), err, 512)
                 if wrc == 0 and support:
                     wrc = host.fighost_run_write_support(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
-                                                         C.cast(raw.ctypes.data, C.c_char_p), api._p(g_sup, api.c_i32_p), api._p(g_org, api.c_i32_p), err, 512)
+                                                         C.cast(raw.ctypes.data, C.c_char_p), api._p(G["sup"], api.c_i32_p), api._p(G["org"], api.c_i32_p), err, 512)
                 if wrc == 0 and quality:
                     wrc = host.fighost_run_write_quality(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
-                                                         api._p(g_phr, api.c_u8_p), api._p(g_qst, api.c_u8_p), err, 512)
+                                                         api._p(G["phr"], api.c_u8_p), api._p(G["qst"], api.c_u8_p), err, 512)
                 if wrc == 0 and placement:
-                    wrc = host.fighost_run_write_placement(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(g_ppq, api.c_u8_p), api._p(g_pst, api.c_u8_p), err, 512)
+                    wrc = host.fighost_run_write_placement(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(G["ppq"], api.c_u8_p), api._p(G["pst"], api.c_u8_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

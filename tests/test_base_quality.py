@@ -87,9 +87,10 @@ def hand_model(mode):
 
 class Hand:
     """A resident batch and a `filled` made by hand.  gaps: per gap (n, unmapped reads, partial reads, evidence 'u' / 'p',
-    draw length of the evidence header, origin)."""
+    draw length of the evidence header, origin).  lens: the read lengths, dealt in turn; last_n: the first read of every length
+    ends in an N."""
 
-    def __init__(self, mode, gaps, seed):
+    def __init__(self, mode, gaps, seed, lens=READ_LENS, last_n=False):
         rng = np.random.default_rng(seed)
         self.mode, self.gaps = mode, gaps
         self.model = hand_model(mode)
@@ -103,10 +104,12 @@ class Hand:
         def reads_of(count, n):
             seqs, offs = [], []
             for r in range(count):
-                ln = READ_LENS[r % 4]
+                ln = lens[r % len(lens)]
                 s = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=ln).copy()
                 if r % 5 == 4:
-                    s[rng.choice(ln, size=2, replace=False)] = ord("N")
+                    s[rng.choice(ln, size=min(ln, 2), replace=False)] = ord("N")
+                if last_n and r < len(lens):
+                    s[-1] = ord("N")
                 seqs.append(s)
                 offs.append(INT_MIN if r % 7 == 6 else int(rng.integers(-ln - 2, n + 3)))
             return seqs, offs
@@ -179,6 +182,30 @@ def hand_unmapped():
 def hand_partial():
     """the partial-mode model: two gaps with 5 and 70 partial reads (one chunk boundary)"""
     return Hand("partial", [(40, 0, 5, "p", 40, F_), (300, 0, 70, "p", 300, F_ | T_)], 77)
+
+
+EDGE_LENS = (1, 16, 17, 32, 33, 199)
+
+
+def hand_edge_lengths():
+    """One gap of 40 columns with 65 unmapped reads (one chunk boundary) of the lengths at which a staged read's layout changes: the
+    2-bit word count at 16 | 17 and 32 | 33, the N-mask word count at 32 | 33, the four-lane word split at 1 (one lane) and 199
+    (all twenty words); the first read of every length ends in an N."""
+    return Hand("unmapped", [(40, 65, 2, "u", 40, F_)], 20261020, lens=EDGE_LENS, last_n=True)
+
+
+def test_edge_length_case_is_valid():
+    """Every length of the edge-length case has a drawn read that overlaps the string of its (on) gap, and a read whose last base
+    is N; the restatement's plane is not trivial."""
+    H = hand_edge_lengths()
+    assert list(H.state) == [1]
+    ev = H.evidence(0)
+    assert len(ev) == 65 and {len(s) for _, s, *_ in ev} == set(EDGE_LENS)
+    for ln in EDGE_LENS:
+        assert any(len(s) == ln and o != INT_MIN and o < 40 and o + ln > 0 for o, s, *_ in ev), f"no drawn read of length {ln} on the string"
+        assert any(len(s) == ln and s[-1] == ord("N") for _, s, *_ in ev), f"no read of length {ln} ends in N"
+    LL = H.expected()
+    assert LL.shape == (40, 4) and LL.any() and not np.isnan(LL).any()
 
 
 def test_hand_case_is_not_vacuous():
@@ -339,6 +366,24 @@ def test_kernel_arithmetic_on_the_cpu(tmp_path):
     assert len(got) == 1 + 257 + 600 and same_bits(got, want)
 
 
+def test_edge_lengths_on_the_cpu(tmp_path):
+    """The edge-length case through the same stand-alone program (tests/quality_column_main.cpp, AddressSanitizer and UBSan): the
+    plane equals the numpy restatement bit for bit."""
+    H = hand_edge_lengths()
+    exe = str(tmp_path / "quality_column")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", "-o", exe, os.path.join(util.ROOT, "tests", "quality_column_main.cpp")])
+    ev = H.evidence(0)
+    lines = ["200", " ".join(float(v).hex() for v in H.model.e), " ".join(float(v).hex() for v in H.model.T), "1", f"40 {len(ev)}"]
+    lines += [f"{o} {len(s)} {part} {aux} {s.tobytes().decode()}" for o, s, part, aux in ev]
+    case = tmp_path / "case.txt"
+    case.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([exe, str(case)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = np.array([int(t, 16) for t in r.stdout.split()], dtype=np.uint64).view(np.float64).reshape(-1, 4)
+    assert same_bits(got, H.expected())
+
+
 def test_figfill_on_a_library_without_the_call_fails_loudly(tmp_path):
     """FIGFILL_QUALITY=1 with the emulation behind figfill: a non-zero exit that names the missing call, and no gapquality.txt."""
     root = util.extract_golden("partial_small", str(tmp_path))
@@ -407,6 +452,13 @@ def test_hand_made_placements_unmapped_model():
 def test_hand_made_placements_partial_model():
     """The same in a partial-mode model (gap_ot_preset given, so the upload probes nothing): 5 and 70 partial reads."""
     _check_hand(hand_partial())
+
+
+@pytest.mark.gpu
+def test_edge_lengths_on_the_device():
+    """fig_batch_quality on the edge-length case (read lengths 1, 16, 17, 32, 33, 199; 65 reads; 40 columns): bit for bit the
+    restatement, and everything else test_hand_made_placements_unmapped_model asks of a hand-made case."""
+    _check_hand(hand_edge_lengths())
 
 
 @pytest.mark.gpu

@@ -161,40 +161,45 @@ class HandPlace:
     """A resident batch and a `filled` made by hand, no fill.  Gap 0 lies 120 bases from the contig start, the last gap ends 100
     bases before the contig end (both fewer than len - 1 for the longer reads: N columns beyond the contig).  A read is a copy of
     the gap's sequence at a true offset with a few substitutions, its anchor chosen so that the true offset has a given insert
-    size; most reads are drawn at the true offset."""
+    size; most reads are drawn at the true offset.  gaps / state: another gap list than GAPS (which alone gets the repeat of gap
+    2, the Ns beside gap 3 and the all -inf read) and the states it is to have; lens: the read lengths, dealt in turn; last_n: the
+    first read of every length ends in an N."""
 
-    def __init__(self, seed=SEED, mode="unmapped"):
+    def __init__(self, seed=SEED, mode="unmapped", gaps=GAPS, state=STATE, lens=READ_LENS, last_n=False):
         rng = np.random.default_rng(seed)
         self.model = place_model(mode)
-        ng = len(GAPS)
+        self.gaps = gaps
+        ng = len(gaps)
         acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
         starts, p = [], 120
         for g in range(ng):
             starts.append(p); p += G0 + 420
         clen = starts[-1] + G0 + 100
         contig = rng.choice(acgt, size=clen).copy()
-        contig[starts[3] - 40] = ord("N"); contig[starts[3] + G0 + 7] = ord("N")           # N in either flank of gap 3
+        if gaps is GAPS:
+            contig[starts[3] - 40] = ord("N"); contig[starts[3] + G0 + 7] = ord("N")       # N in either flank of gap 3
         self.starts = np.array(starts, dtype=np.int64)
-        self.filled_len = np.array([g[0] for g in GAPS], dtype=np.int32)
+        self.filled_len = np.array([g[0] for g in gaps], dtype=np.int32)
         self.str_off = np.concatenate([[0], np.cumsum(self.filled_len)]).astype(np.int64)
         self.raw = rng.choice(np.frombuffer(b"ACGTACGTACGTACGTACGTN", dtype=np.uint8), size=int(self.str_off[-1])).copy()
-        a = int(self.str_off[2])         # gap 2: the second half of the string repeats the first but for five bases, so that reads
-        self.raw[a + 128:a + 256] = self.raw[a:a + 128]                        # there have a second placement one or two substitutions away
-        for x in (5, 40, 47, 90, 121):
-            self.raw[a + 128 + x] = acgt[(int(CODE[self.raw[a + x]]) + 1 + x % 3) % 4]
-        tg = [g for g in range(ng) if GAPS[g][6] == "tandem"][0]
+        a = int(self.str_off[2]) if gaps is GAPS else None
+        if a is not None:                # gap 2: the second half of the string repeats the first but for five bases, so that reads
+            self.raw[a + 128:a + 256] = self.raw[a:a + 128]                    # there have a second placement one or two substitutions away
+            for x in (5, 40, 47, 90, 121):
+                self.raw[a + 128 + x] = acgt[(int(CODE[self.raw[a + x]]) + 1 + x % 3) % 4]
         ph = lambda x: UNIT[np.mod(x, 12)]
-        contig[starts[tg] - 300:starts[tg]] = ph(np.arange(-300, 0))
-        contig[starts[tg] + G0:starts[tg] + G0 + 300] = ph(GAPS[tg][0] + np.arange(300))
-        self.raw[int(self.str_off[tg]):int(self.str_off[tg + 1])] = ph(np.arange(GAPS[tg][0]))
+        for tg in [g for g in range(ng) if gaps[g][6] == "tandem"]:
+            contig[starts[tg] - 300:starts[tg]] = ph(np.arange(-300, 0))
+            contig[starts[tg] + G0:starts[tg] + G0 + 300] = ph(gaps[tg][0] + np.arange(300))
+            self.raw[int(self.str_off[tg]):int(self.str_off[tg + 1])] = ph(np.arange(gaps[tg][0]))
         for st in starts:
             contig[st:st + G0] = ord("N")
         self.contig = contig
         self.S = [columns(contig, starts[g], G0, self.raw[int(self.str_off[g]):int(self.str_off[g + 1])]) for g in range(ng)]
         u_off, p_off, seqs, pos, rev, draw, pseqs = [0], [0], [], [], [], [], []
-        for g, (n, nu, npart, ev, dl, org, what) in enumerate(GAPS):
+        for g, (n, nu, npart, ev, dl, org, what) in enumerate(gaps):
             for r in range(nu):
-                ln = (31, 31, 31, 77, 77, 31)[r] if what == "tandem" else READ_LENS[r % 4]
+                ln = (31, 31, 31, 77, 77, 31)[r] if what == "tandem" else lens[r % len(lens)]
                 t = int(rng.integers(-(ln - 1), n))
                 s = np.frombuffer(b"ACGTN", dtype=np.uint8)[self.S[g][199 + t + np.arange(ln)]].copy()
                 s[s == ord("N")] = rng.choice(acgt, size=int((s == ord("N")).sum()))
@@ -202,9 +207,11 @@ class HandPlace:
                 if what == "tandem":
                     I = 800
                 else:
-                    s[rng.choice(ln, size=int(rng.integers(0, 4)), replace=False)] = rng.choice(acgt)
+                    s[rng.choice(ln, size=min(ln, int(rng.integers(0, 4))), replace=False)] = rng.choice(acgt)
                     if r % 5 == 4:
-                        s[rng.choice(ln, size=2, replace=False)] = ord("N")
+                        s[rng.choice(ln, size=min(ln, 2), replace=False)] = ord("N")
+                    if last_n and r < len(lens):
+                        s[-1] = ord("N")
                     I = int(rng.integers(150, 1001))
                     if r % 17 == 16:
                         I = 5000                                      # no valid placement at all
@@ -232,12 +239,13 @@ class HandPlace:
         # the read whose every valid placement is -inf: read 1 of gap 0 (n = 1, length 77, reversed: k = 17 is base 59, left
         # anchor) gets the anchor that leaves it the three placements -2, -1, 0 (insert sizes 150, 151, 152), is drawn at 0, and
         # gets at base 59 a base that differs from the three columns under it: e[17] = 0 makes each of them -inf
-        assert len(seqs[1]) == 77 and rev[1] == 1
-        pos[1] = starts[0] + 77 - 152; draw[1] = 0
-        under = {int(c) for c in self.S[0][199 + 59 + np.array([-2, -1, 0])]}
-        assert 4 not in under
-        seqs[1][59] = acgt[min(set(range(4)) - under)]
-        seqs[1][seqs[1] == ord("N")] = ord("A")
+        if gaps is GAPS:
+            assert len(seqs[1]) == 77 and rev[1] == 1
+            pos[1] = starts[0] + 77 - 152; draw[1] = 0
+            under = {int(c) for c in self.S[0][199 + 59 + np.array([-2, -1, 0])]}
+            assert 4 not in under
+            seqs[1][59] = acgt[min(set(range(4)) - under)]
+            seqs[1][seqs[1] == ord("N")] = ord("A")
         self.NU, NP = u_off[-1], p_off[-1]
         cat = lambda v: np.concatenate(v) if v else np.zeros(1, dtype=np.uint8)
         soff = lambda v: np.concatenate([[0], np.cumsum([len(s) for s in v])]).astype(np.int64)
@@ -256,14 +264,14 @@ class HandPlace:
         self.draw_pos = i32((draw if nu_planes else []) + [5] * NP)
         self.draw_isz = np.zeros(len(self.draw_pos), dtype=np.int32)
         self.draw_len = np.full(2 * ng, -1, dtype=np.int32)
-        for g, (n, _, _, ev, dl, _, _) in enumerate(GAPS):
+        for g, (n, _, _, ev, dl, _, _) in enumerate(gaps):
             self.draw_len[2 * g + (1 if ev == "p" else 0)] = dl
-        self.origin = np.array([g[5] for g in GAPS], dtype=np.int32)
-        self.state = np.array(STATE if mode == "unmapped" else [0] * ng, dtype=np.uint8)
+        self.origin = np.array([g[5] for g in gaps], dtype=np.int32)
+        self.state = np.array(state if mode == "unmapped" else [0] * ng, dtype=np.uint8)
 
     def scored(self):
         out = np.zeros(self.NU, dtype=bool)
-        for g in range(len(GAPS)):
+        for g in range(len(self.gaps)):
             if self.state[g]:
                 for k in range(int(self.u_off[g]), int(self.u_off[g + 1])):
                     out[k] = self.draw_pos[k] != INT_MIN
@@ -274,7 +282,7 @@ class HandPlace:
         tabs = place_tables(self.model.cstruct())
         w = unscored(self.NU)
         sc = self.scored()
-        for g in range(len(GAPS)):
+        for g in range(len(self.gaps)):
             for k in range(int(self.u_off[g]), int(self.u_off[g + 1])):
                 if sc[k]:
                     r = restate_read(self.S[g], int(self.filled_len[g]), self.seqs[k], int(self.rev[k]), self.pos[k], int(self.draw_pos[k]), int(self.starts[g]), G0, tabs)
@@ -292,6 +300,29 @@ def hand():
     """the hand-made case and its restatement: built once, never modified"""
     H = HandPlace()
     return H, H.expected()
+
+
+EDGE_LENS = tbq.EDGE_LENS
+
+
+@pytest.fixture(scope="module")
+def hand_edge():
+    """One gap of 40 columns with 65 unmapped reads (one chunk boundary) of the lengths at which a staged read's layout changes
+    (tbq.hand_edge_lengths), the first read of every length ending in an N; and its restatement.  Built once, never modified."""
+    H = HandPlace(seed=20261020, gaps=[(40, 65, 0, "u", 40, F_, "")], state=[1], lens=EDGE_LENS, last_n=True)
+    return H, H.expected()
+
+
+def test_edge_length_case_is_valid(hand_edge):
+    """Every length of the edge-length case has a scored read drawn on the string with a valid drawn placement, and a read whose
+    last base is N."""
+    H, W = hand_edge
+    sc = H.scored()
+    assert list(H.state) == [1] and H.NU == 65 and {len(s) for s in H.seqs} == set(EDGE_LENS)
+    for ln in EDGE_LENS:
+        ks = [k for k in range(65) if len(H.seqs[k]) == ln]
+        assert any(sc[k] and -(ln - 1) <= H.draw_pos[k] <= 39 and np.isfinite(W["ll_drawn"][k]) and W["n_valid"][k] > 1 for k in ks), f"no scored read of length {ln} on the string"
+        assert any(H.seqs[k][-1] == ord("N") for k in ks), f"no read of length {ln} ends in N"
 
 
 def test_hand_case_is_not_vacuous(hand):
@@ -540,6 +571,32 @@ def test_kernel_arithmetic_on_the_cpu(hand, tmp_path):
     assert [int(t[2]) for t in rows] == list(W["off_other"][sc]) and [int(t[3]) for t in rows] == list(W["n_valid"][sc])
 
 
+def test_edge_lengths_on_the_cpu(hand_edge, tmp_path):
+    """The edge-length case through the same stand-alone program (tests/placement_read_main.cpp, AddressSanitizer and UBSan):
+    ll_drawn, ll_other, off_other and n_valid equal the numpy restatement bit for bit."""
+    H, W = hand_edge
+    exe = str(tmp_path / "placement_read")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", "-o", exe, os.path.join(util.ROOT, "tests", "placement_read_main.cpp")])
+    m = H.model
+    st = int(H.starts[0])
+    left = [CODE[H.contig[st - k]] if st - k >= 0 else 4 for k in range(1, FLANK + 1)]
+    right = [CODE[H.contig[st + G0 + k]] if st + G0 + k < len(H.contig) else 4 for k in range(FLANK)]
+    lines = ["200", " ".join(float(v).hex() for v in m.e), " ".join(float(v).hex() for v in m.T), f"{len(m.insd)} {m.Tmin} {m.Tmax}",
+             " ".join(float(v).hex() for v in m.insd), "1", f"40 {st} {G0} {H.NU}", "".join(str(int(c)) for c in left + right), H.raw.tobytes().decode()]
+    lines += [f"{int(H.draw_pos[k])} {len(H.seqs[k])} {int(H.rev[k])} {H.pos[k]} {H.seqs[k].tobytes().decode()}" for k in range(H.NU)]
+    case = tmp_path / "case.txt"
+    case.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([exe, str(case)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    rows = [ln.split() for ln in r.stdout.splitlines()]
+    sc = np.flatnonzero(H.scored())
+    assert len(rows) == len(sc) > 40
+    assert same_bits(np.array([int(t[0], 16) for t in rows], dtype=np.uint64).view(np.float64), W["ll_drawn"][sc])
+    assert same_bits(np.array([int(t[1], 16) for t in rows], dtype=np.uint64).view(np.float64), W["ll_other"][sc])
+    assert [int(t[2]) for t in rows] == list(W["off_other"][sc]) and [int(t[3]) for t in rows] == list(W["n_valid"][sc])
+
+
 # ------------------------------------------------------------------------------------- GPU
 def _placement_raw(eng, H, origin, nu=None):
     """fig_batch_placement through ctypes with the caller's buffers filled with 0xFF bytes before the call"""
@@ -553,7 +610,7 @@ def _placement_raw(eng, H, origin, nu=None):
     for a in d:
         a.view(np.uint8)[...] = 0xFF
     off = np.full(m, -1, dtype=np.int32); nv = np.full(m, -1, dtype=np.int32); pq = np.full(m, 0xFF, dtype=np.uint8); pq[::2] = 0xFE
-    st = np.full(len(GAPS), 0xFF, dtype=np.uint8)
+    st = np.full(len(H.gaps), 0xFF, dtype=np.uint8)
     rp = api.FigReadPlacement()
     rp.ll_drawn = api._p(d[0], api.c_double_p); rp.ll_other = api._p(d[1], api.c_double_p); rp.sum_other = api._p(d[2], api.c_double_p)
     rp.off_other = api._p(off, api.c_i32_p); rp.n_valid = api._p(nv, api.c_i32_p); rp.pq = api._p(pq, api.c_u8_p); rp.state = api._p(st, api.c_u8_p)
@@ -600,6 +657,22 @@ def test_hand_made_batch(hand):
     finally:
         eng.close()
     assert "libfighip.so" in open("/proc/self/maps").read()
+
+
+@pytest.mark.gpu
+def test_edge_lengths_on_the_device(hand_edge):
+    """fig_batch_placement on the resident edge-length case (read lengths 1, 16, 17, 32, 33, 199; 65 reads; 40 columns): the exact
+    outputs bit for bit the restatement's, sum_other inside its bound, pq as defined; buffers came in as 0xFF bytes."""
+    H, W = hand_edge
+    eng = api.Engine(0)
+    try:
+        eng.set_model(H.model)
+        eng.upload(H.batch)
+        rc, P = _placement_raw(eng, H, H.origin)
+    finally:
+        eng.close()
+    assert rc == 0 and list(P.state) == [1]
+    compare(P, W, H.scored())
 
 
 @pytest.mark.gpu
