@@ -95,6 +95,25 @@ class Placement:
     state: np.ndarray
 
 
+class FigGapSoftqual(C.Structure):
+    _fields_ = [("wcount", c_double_p), ("eloglik", c_double_p), ("phred", c_u8_p), ("state", c_u8_p)]
+
+
+# fig_gap_softqual::state (include/figbird_hip.h)
+SOFTQ_OFF, SOFTQ_ON = 0, 1
+
+
+@dataclass
+class SoftQual:
+    """fig_gap_softqual of one call: the planes are indexed like the strings (base x of gap g at str_off[g] + x), state per gap;
+    placement: the fig_read_placement of the same call, when asked for"""
+    wcount: np.ndarray
+    eloglik: np.ndarray
+    phred: np.ndarray
+    state: np.ndarray
+    placement: Optional[Placement] = None
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -104,7 +123,8 @@ class FigStats(C.Structure):
 
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
            "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
-           "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality", "fig_batch_placement"]
+           "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality", "fig_batch_placement",
+           "fig_batch_softqual"]
 
 _lib = None
 _host = None
@@ -142,6 +162,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.fig_batch_quality.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigGapQuality)]
     if hasattr(lib, "fig_batch_placement"):           # (likewise)
         lib.fig_batch_placement.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigReadPlacement)]
+    if hasattr(lib, "fig_batch_softqual"):            # (likewise)
+        lib.fig_batch_softqual.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigReadPlacement), C.POINTER(FigGapSoftqual)]
     if path is None:
         _lib = lib
     return lib
@@ -177,6 +199,10 @@ def load_host_library() -> C.CDLL:
         _host.fighost_placement_phred.argtypes = [C.c_int64, c_double_p, c_double_p, c_double_p, c_u8_p]
         _host.fighost_placement_gaps_on.argtypes = [C.c_int, C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
         _host.fighost_run_write_placement.argtypes = [C.c_void_p, c_i32_p, c_u8_p, c_u8_p, C.c_char_p, C.c_int]
+        _host.fighost_softqual_gaps_on.argtypes = [C.c_int, C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
+        _host.fighost_softqual_active.argtypes = [C.c_double]
+        _host.fighost_softqual_mz.argtypes = [C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_u8_p]
+        _host.fighost_run_write_softquality.argtypes = [C.c_void_p, c_i32_p, c_i64_p, c_u8_p, c_u8_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -323,6 +349,7 @@ class FillResult:
     support_origin: Optional[np.ndarray] = None   # int32 [n_gaps]: SUP_* mask (fig_gap_support::origin)
     placement: Optional["Placement"] = None   # fig_read_placement of the fill's drawn unmapped reads, when requested
     quality: Optional[tuple] = None        # (loglik float64 [total, 4], phred uint8 [total], state uint8 [n_gaps]) of fig_gap_quality, indexed like raw
+    softqual: Optional["SoftQual"] = None  # fig_gap_softqual of the fill's strings, when requested
 
     @property
     def filled_bases(self) -> int:
@@ -426,6 +453,13 @@ class Engine:
         if len(keep[3]) < nu:
             raise ValueError("placement: one drawn offset per unmapped read of the resident batch")
         org, org_p = self._origin_arg("placement", origin)
+        rp, out = self._placement_buffers(n, nu)
+        self._check(self.lib.fig_batch_placement(self.ctx, C.byref(r), org_p, C.byref(rp)), "fig_batch_placement")
+        return out
+
+    @staticmethod
+    def _placement_buffers(n: int, nu: int):
+        """a fig_read_placement over fresh 0xFF-filled arrays for n gaps and nu unmapped reads -> (the struct, the Placement of their views)"""
         m = max(nu, 1)
         d = [np.zeros(m) for _ in range(3)]
         for a in d:
@@ -435,8 +469,26 @@ class Engine:
         rp = FigReadPlacement()
         rp.ll_drawn = _p(d[0], c_double_p); rp.ll_other = _p(d[1], c_double_p); rp.sum_other = _p(d[2], c_double_p)
         rp.off_other = _p(off, c_i32_p); rp.n_valid = _p(nv, c_i32_p); rp.pq = _p(pq, c_u8_p); rp.state = _p(stt, c_u8_p)
-        self._check(self.lib.fig_batch_placement(self.ctx, C.byref(r), org_p, C.byref(rp)), "fig_batch_placement")
-        return Placement(d[0][:nu], d[1][:nu], d[2][:nu], off[:nu], nv[:nu], pq[:nu], stt[:n])
+        return rp, Placement(d[0][:nu], d[1][:nu], d[2][:nu], off[:nu], nv[:nu], pq[:nu], stt[:n])
+
+    def softqual(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: bool = False) -> "SoftQual":
+        """fig_batch_softqual of the strings and draw planes in `res` against the resident batch; `origin` as for quality().
+        placement=True: the fig_read_placement of the same call as well (SoftQual.placement).  The buffers handed to the library
+        start as 0xFF bytes, so that an element it failed to write shows."""
+        self._need("fig_batch_softqual", "softqual")
+        r, keep = self._filled_struct("softqual", res)
+        n, nu = self.n_gaps, self._n_ureads()
+        if len(keep[3]) < nu:
+            raise ValueError("softqual: one drawn offset per unmapped read of the resident batch")
+        total = int(keep[1][n])
+        org, org_p = self._origin_arg("softqual", origin)
+        wc = np.zeros((max(total, 1), 4)); wc.view(np.uint8)[...] = 0xFF
+        el = np.zeros((max(total, 1), 4)); el.view(np.uint8)[...] = 0xFF
+        ph = np.full(max(total, 1), 0xFF, dtype=np.uint8); stt = np.full(max(n, 1), 0xFF, dtype=np.uint8)
+        sq = FigGapSoftqual(); sq.wcount = _p(wc, c_double_p); sq.eloglik = _p(el, c_double_p); sq.phred = _p(ph, c_u8_p); sq.state = _p(stt, c_u8_p)
+        rp, plc = self._placement_buffers(n, nu) if placement else (None, None)
+        self._check(self.lib.fig_batch_softqual(self.ctx, C.byref(r), org_p, C.byref(rp) if placement else None, C.byref(sq)), "fig_batch_softqual")
+        return SoftQual(wc[:total], el[:total], ph[:total], stt[:n], plc)
 
     def quality(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: Optional["Placement"] = None, min_pq: Optional[int] = None):
         """fig_batch_quality of the strings and draw planes in `res` against the resident batch; `origin` is
@@ -463,13 +515,15 @@ class Engine:
         self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), org_p, C.byref(gq)), "fig_batch_quality")
         return ll[:total], ph[:total], stt[:n]
 
-    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool):
-        """quality and placement need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False):
+        """quality, placement and softqual need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
         if quality:
             self._need("fig_batch_quality", "quality=True")
         if placement:
             self._need("fig_batch_placement", "placement=True")
-        return draw or quality or placement, support or quality or placement
+        if softqual:
+            self._need("fig_batch_softqual", "softqual=True")
+        return draw or quality or placement or softqual, support or quality or placement or softqual
 
     def _result_arrays(self, n: int, cap: int, nr: Optional[int], draw: bool):
         """Fresh result arrays for n gaps and cap string bytes and, unless nr is None, draw planes for nr reads, behind a
@@ -486,19 +540,20 @@ class Engine:
             r.draw_pos = _p(planes[0], c_i32_p); r.draw_isz = _p(planes[1], c_i32_p); r.draw_len = _p(planes[2], c_i32_p)
         return r, fl, gt, so, st, planes
 
-    def _post_fill(self, filled: FillResult, placement: bool, quality: bool, min_pq: Optional[int] = None):
-        """the passes beside a fill whose batch is still resident, with its origins -> (Placement or None, quality or None)"""
+    def _post_fill(self, filled: FillResult, placement: bool, quality: bool, min_pq: Optional[int] = None, softqual: bool = False):
+        """the passes beside a fill whose batch is still resident, with its origins -> (Placement or None, quality or None, SoftQual or None)"""
         plc = self.placement(filled, filled.support_origin) if placement else None
         qual = None
         if quality:
             qual = self.quality(filled, filled.support_origin, placement=plc if min_pq is not None else None, min_pq=min_pq)
-        return plc, qual
+        return plc, qual, (self.softqual(filled, filled.support_origin) if softqual else None)
 
     def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-                      placement: bool = False) -> FillResult:
+                      placement: bool = False, softqual: bool = False) -> FillResult:
         """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins);
-        placement=True likewise fills FillResult.placement (fig_batch_placement with the origins)."""
-        draw, support = self._implied(support, draw, quality, placement)
+        placement=True likewise fills FillResult.placement (fig_batch_placement with the origins), softqual=True
+        FillResult.softqual (fig_batch_softqual with the origins)."""
+        draw, support = self._implied(support, draw, quality, placement, softqual)
         n = self.n_gaps
         nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1]) if draw else None
         r, fl, gt, so, st, planes = self._result_arrays(n, self.cap, nr, draw)
@@ -533,7 +588,7 @@ class Engine:
             res.draw = (planes[0][:nr], planes[1][:nr], planes[2][:2 * n])
         if support:
             res.support = sup_c[:int(so[n])]; res.support_origin = sup_o[:n]
-        res.placement, res.quality = self._post_fill(res, placement, quality)
+        res.placement, res.quality, res.softqual = self._post_fill(res, placement, quality, softqual=softqual)
         return res
 
     def free_batch(self):
@@ -563,17 +618,18 @@ class Engine:
             self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
 
     def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False, quality: bool = False,
-                    keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None) -> FillResult:
+                    keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None, softqual: bool = False) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
         resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
         read support as well (fields `support`, `support_origin`).  quality=True implies draw and support and runs
         fig_batch_quality before the batch is freed (field `quality`).  keep_resident=True leaves an uploaded batch resident
         for a further call.  placement=True likewise runs fig_batch_placement (field `placement`); with min_pq as well the
-        quality leaves out the scored reads below that pq (Engine.quality)."""
-        draw, support = self._implied(support, draw, quality, placement or min_pq is not None)
+        quality leaves out the scored reads below that pq (Engine.quality).  softqual=True likewise runs fig_batch_softqual (field
+        `softqual`)."""
+        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual)
         placement = placement or min_pq is not None
-        qual = plc = None
+        qual = plc = sq = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         nr = n_ureads + n_preads
@@ -587,9 +643,9 @@ class Engine:
         if n > 0 and resident:
             try:
                 sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
-                if placement or quality:
+                if placement or quality or softqual:
                     self.n_gaps = n; self._cb = cbatch
-                    plc, qual = self._post_fill(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), placement, quality, min_pq)
+                    plc, qual, sq = self._post_fill(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), placement, quality, min_pq, softqual)
             finally:
                 if not keep_resident:
                     self.lib.fig_batch_free(self.ctx)
@@ -605,13 +661,15 @@ class Engine:
         if placement:
             z = np.zeros(0)
             res.placement = plc if plc is not None else Placement(z, z, z, np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
+        if softqual:
+            res.softqual = sq if sq is not None else SoftQual(np.zeros((0, 4)), np.zeros((0, 4)), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
         return res
 
     def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-             placement: bool = False) -> FillResult:
+             placement: bool = False, softqual: bool = False) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual)
         finally:
             self.free_batch()
 

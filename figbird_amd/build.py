@@ -76,7 +76,8 @@ def build_figfill(force: bool = False) -> str:
     host, hdrs, libs = _host_sources()
     main_cpp = os.path.join(host, "figfill_main.cpp")
     srcs = hdrs + libs + [main_cpp, os.path.join(ROOT, "include", "figbird_hip.h"), os.path.join(CSRC, "fig_gaprules.h"),
-                          os.path.join(CSRC, "fig_quality_host.h"), os.path.join(CSRC, "fig_placement_host.h")]      # (figtool_main.cpp is built below)
+                          os.path.join(CSRC, "fig_quality_host.h"), os.path.join(CSRC, "fig_placement_host.h"),
+                          os.path.join(CSRC, "fig_softqual_host.h")]      # (figtool_main.cpp is built below)
     common = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread"]
     if force or not _newer(FIGFILL, srcs + [LIB]):
         _run(common + ["-o", FIGFILL, main_cpp] + libs + ["-L" + LIBDIR, "-lfighip", "-Wl,-rpath,$ORIGIN/../lib"])

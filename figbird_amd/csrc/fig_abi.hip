@@ -23,6 +23,7 @@
 #include "fig_quality.h"
 #include "fig_quality_host.h"
 #include "fig_placement.h"
+#include "fig_softqual.h"
 
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
@@ -868,43 +869,47 @@ extern "C" int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *f, const i
     return FIG_OK;
 }
 
-// Placement confidence per drawn unmapped read (fig_placement.h: the kernel; fig_placement_host.h: li, insert size, validity, which
-// gaps are on, Phred)
-extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_read_placement *p) {
-    if (!p || !p->ll_drawn || !p->ll_other || !p->sum_other || !p->off_other || !p->n_valid || !p->pq || !p->state) return FIG_EINVAL;
-    FigPostFill P;
-    std::vector<double> insd;
-    FIG_TRY(P.open(ctx, f, &insd));
-    const int64_t ng = ctx->n_gaps, nu = ctx->n_ureads;
-    const FigDevBatch &db = ctx->db;
-    const int MI = ctx->dm.max_insert;
-    std::vector<double> li((size_t)MI);
-    fig_placement_li(MI, insd.data(), li.data());
-    // which gaps are on, their work items, and the bounds of what the kernel will index with
-    std::vector<int32_t> items;
-    std::vector<int32_t> ncol((size_t)std::max<int64_t>(ng, 1), 0);
-    std::vector<uint8_t> scored((size_t)std::max<int64_t>(nu, 1), 0);
-    int64_t gaps_on = 0, reads = 0, placements = 0;
-    for (int64_t g = 0; g < ng; g++) {
-        const int32_t n = f->filled_len[g];
-        p->state[g] = fig_placement_gap_on(ctx->dm.unmapped != 0, n, f->draw_len[2 * g], f->draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
-        if (p->state[g] != FIG_PLACE_ON) continue;
-        const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
-        const int64_t drawn = P.drawn_reads(g, n, base, cnt, nu);
-        if (drawn < 0) return FIG_EINVAL;
-        gaps_on++; ncol[(size_t)g] = n; reads += drawn;
-        for (int64_t r = 0; r < cnt; r++) scored[(size_t)(base + r)] = f->draw_pos[base + r] != INT32_MIN;
-        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {              // a chunk without a drawn read is no work item
-            bool any = false;
-            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) any = any || scored[(size_t)(base + r)];
-            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
+// The placement pass as fig_batch_placement and fig_batch_softqual both run it: prepare() decides which gaps are on, bounds what the
+// kernel will index with, lists the work items and uploads; launch() is the kernel; fetch() / finish() bring the five arrays back
+// and fill the caller's struct.
+struct FigPlacePass {
+    std::vector<int32_t> items, ncol;
+    std::vector<uint8_t> scored, state;
+    std::vector<double> li, hd;
+    std::vector<int32_t> hi;
+    int64_t gaps_on = 0, reads = 0, placements = 0, cols = 0, nu = 0;
+    FigPlaceArgs A;
+    double *dd = nullptr;
+    int32_t *di = nullptr;
+
+    int prepare(FigPostFill &P, const int32_t *origin, const std::vector<double> &insd) {
+        fig_ctx *ctx = P.ctx;
+        const fig_gap_results *f = P.f;
+        const int64_t ng = ctx->n_gaps;
+        const FigDevBatch &db = ctx->db;
+        const int MI = ctx->dm.max_insert;
+        nu = ctx->n_ureads;
+        li.resize((size_t)MI);
+        fig_placement_li(MI, insd.data(), li.data());
+        ncol.assign((size_t)std::max<int64_t>(ng, 1), 0);
+        state.assign((size_t)std::max<int64_t>(ng, 1), FIG_PLACE_OFF);
+        scored.assign((size_t)std::max<int64_t>(nu, 1), 0);
+        for (int64_t g = 0; g < ng; g++) {
+            const int32_t n = f->filled_len[g];
+            state[(size_t)g] = fig_placement_gap_on(ctx->dm.unmapped != 0, n, f->draw_len[2 * g], f->draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+            if (state[(size_t)g] != FIG_PLACE_ON) continue;
+            const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
+            const int64_t drawn = P.drawn_reads(g, n, base, cnt, nu);
+            if (drawn < 0) return FIG_EINVAL;
+            gaps_on++; ncol[(size_t)g] = n; reads += drawn; cols += n;
+            for (int64_t r = 0; r < cnt; r++) scored[(size_t)(base + r)] = f->draw_pos[base + r] != INT32_MIN;
+            for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {              // a chunk without a drawn read is no work item
+                bool any = false;
+                for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) any = any || scored[(size_t)(base + r)];
+                if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
+            }
         }
-    }
-    for (int64_t r = 0; r < nu; r++) {
-        p->ll_drawn[r] = 0.0; p->ll_other[r] = 0.0; p->sum_other[r] = 0.0; p->off_other[r] = INT32_MIN; p->n_valid[r] = 0; p->pq[r] = FIG_PLACE_NONE;
-    }
-    if (!items.empty()) {
-        FigPlaceArgs A;
+        if (items.empty()) return FIG_OK;
         A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_pos = db.u.pos; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank;
         A.L = ctx->dm.L; A.Tmin = ctx->dm.Tmin; A.Tmax = ctx->dm.Tmax; A.max_insert = MI;
         A.draw_pos = P.up(f->draw_pos, (size_t)nu);
@@ -914,13 +919,22 @@ extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const
         A.str = P.up(f->str, (size_t)P.total);
         A.tabs = P.up(P.tabs.data(), P.tabs.size());
         A.li = P.up(li.data(), li.size());
-        double *dd = (double *)P.alloc((size_t)nu * 3 * sizeof(double));
-        int32_t *di = (int32_t *)P.alloc((size_t)nu * 2 * sizeof(int32_t));
+        dd = (double *)P.alloc((size_t)nu * 3 * sizeof(double));
+        di = (int32_t *)P.alloc((size_t)nu * 2 * sizeof(int32_t));
         A.ll_drawn = dd; A.ll_other = dd + nu; A.sum_other = dd + 2 * nu; A.off_other = di; A.n_valid = di + nu;
-        std::vector<double> hd((size_t)nu * 3);
-        std::vector<int32_t> hi((size_t)nu * 2);
-        FIG_TRY(P.run([&] { hipLaunchKernelGGL(fig_placement_kernel, dim3((unsigned)(items.size() / 2)), dim3(FIG_P_NT), 0, ctx->stream, A); },
-                      [&] { const hipError_t e = P.fetch(hd.data(), dd, hd.size() * sizeof(double)); return e != hipSuccess ? e : P.fetch(hi.data(), di, hi.size() * sizeof(int32_t)); }));
+        hd.resize((size_t)nu * 3); hi.resize((size_t)nu * 2);
+        return FIG_OK;
+    }
+    void launch(hipStream_t stream) { hipLaunchKernelGGL(fig_placement_kernel, dim3((unsigned)(items.size() / 2)), dim3(FIG_P_NT), 0, stream, A); }
+    hipError_t fetch(FigPostFill &P) { const hipError_t e = P.fetch(hd.data(), dd, hd.size() * sizeof(double)); return e != hipSuccess ? e : P.fetch(hi.data(), di, hi.size() * sizeof(int32_t)); }
+    // the caller's struct: the unscored reads' values everywhere, then what the kernel left for the scored ones (`launched`: fetch() has run)
+    void finish(fig_read_placement *p, int64_t ng, bool launched) {
+        for (int64_t g = 0; g < ng; g++) p->state[g] = state[(size_t)g];
+        for (int64_t r = 0; r < nu; r++) {
+            p->ll_drawn[r] = 0.0; p->ll_other[r] = 0.0; p->sum_other[r] = 0.0; p->off_other[r] = INT32_MIN; p->n_valid[r] = 0; p->pq[r] = FIG_PLACE_NONE;
+        }
+        placements = 0;
+        if (!launched) return;
         for (int64_t r = 0; r < nu; r++) {
             if (!scored[(size_t)r]) continue;
             p->ll_drawn[r] = hd[(size_t)r]; p->ll_other[r] = hd[(size_t)(nu + r)]; p->sum_other[r] = hd[(size_t)(2 * nu + r)];
@@ -929,8 +943,84 @@ extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const
             placements += p->n_valid[r];
         }
     }
+};
+static bool fig_placement_members(const fig_read_placement *p) { return p->ll_drawn && p->ll_other && p->sum_other && p->off_other && p->n_valid && p->pq && p->state; }
+
+// Placement confidence per drawn unmapped read (fig_placement.h: the kernel; fig_placement_host.h: li, insert size, validity, which
+// gaps are on, Phred)
+extern "C" int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_read_placement *p) {
+    if (!p || !fig_placement_members(p)) return FIG_EINVAL;
+    FigPostFill P;
+    std::vector<double> insd;
+    FIG_TRY(P.open(ctx, f, &insd));
+    FigPlacePass PP;
+    FIG_TRY(PP.prepare(P, origin, insd));
+    const bool work = !PP.items.empty();
+    if (work) FIG_TRY(P.run([&] { PP.launch(ctx->stream); }, [&] { return PP.fetch(P); }));
+    PP.finish(p, ctx->n_gaps, work);
     if (fig_knobs_from_env(ctx->dm.unmapped).log)
-        fprintf(stderr, "[figplace] gaps on %lld of %lld, reads scored %lld, placements scored %lld, kernel %.3f ms\n", (long long)gaps_on, (long long)ng, (long long)reads, (long long)placements, P.ms);
+        fprintf(stderr, "[figplace] gaps on %lld of %lld, reads scored %lld, placements scored %lld, kernel %.3f ms\n", (long long)PP.gaps_on, (long long)ctx->n_gaps, (long long)PP.reads, (long long)PP.placements, P.ms);
+    return FIG_OK;
+}
+
+// Per-base quality summed over read placements (fig_softqual.h: the kernel; fig_softqual_host.h: which gaps are on, the cut, M / Z):
+// the placement pass into per-call buffers, then the pass that reads them, back to back on the library's stream.
+extern "C" int fig_batch_softqual(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_read_placement *pl, fig_gap_softqual *out) {
+    if (!out || !out->wcount || !out->eloglik || !out->phred || !out->state) return FIG_EINVAL;
+    if (pl && !fig_placement_members(pl)) return FIG_EINVAL;
+    FigPostFill P;
+    std::vector<double> insd;
+    FIG_TRY(P.open(ctx, f, &insd));
+    FigPlacePass PP;
+    FIG_TRY(PP.prepare(P, origin, insd));
+    const int64_t ng = ctx->n_gaps, total = P.total;
+    for (int64_t g = 0; g < ng; g++) out->state[g] = PP.state[(size_t)g] == FIG_PLACE_ON ? FIG_SOFTQ_ON : FIG_SOFTQ_OFF;
+    if (total > 0) { memset(out->wcount, 0, (size_t)total * 4 * sizeof(double)); memset(out->eloglik, 0, (size_t)total * 4 * sizeof(double)); memset(out->phred, 0, (size_t)total); }
+    const bool work = !PP.items.empty();
+    float ms_place = 0, ms_soft = 0;
+    int64_t active = 0;
+    if (work) {
+        std::vector<int32_t> blocks;                             // {gap, first column} of every block of 256 columns of every gap that is on
+        for (int64_t g = 0; g < ng; g++)
+            if (PP.state[(size_t)g] == FIG_PLACE_ON) for (int32_t xb = 0; xb < PP.ncol[(size_t)g]; xb += FIG_SQ_NT) { blocks.push_back((int32_t)g); blocks.push_back(xb); }
+        const size_t nb = blocks.size() / 2, plane = (size_t)total * 4;
+        FigSoftqArgs A;
+        const FigPlaceArgs &Q = PP.A;
+        A.gaps = Q.gaps; A.u_len = Q.u_len; A.u_aux = Q.u_aux; A.u_pos = Q.u_pos; A.u_woff = Q.u_woff; A.packed = Q.packed; A.flank = Q.flank;
+        A.draw_pos = Q.draw_pos; A.ncol = Q.ncol; A.str_off = Q.str_off; A.str = Q.str; A.tabs = Q.tabs; A.li = Q.li;
+        A.L = Q.L; A.Tmin = Q.Tmin; A.Tmax = Q.Tmax; A.max_insert = Q.max_insert;
+        A.placed = PP.dd; A.n_ureads = PP.nu;
+        A.items = P.up(blocks.data(), blocks.size());
+        double *dp = (double *)P.alloc(plane * 2 * sizeof(double) + nb * sizeof(int32_t));
+        A.out = dp; A.plane = (int64_t)plane;
+        std::vector<int32_t> hact(nb, 0);
+        struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) hipEventDestroy(e); } } mid;       // between the two launches
+        if (P.oom) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
+        FIG_HIP(hipEventCreate(&mid.e));
+        FIG_HIP(hipMemsetAsync(dp, 0, plane * 2 * sizeof(double), ctx->stream));
+        FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        PP.launch(ctx->stream);
+        FIG_HIP(hipGetLastError());
+        FIG_HIP(hipEventRecord(mid.e, ctx->stream));
+        hipLaunchKernelGGL(fig_softqual_kernel, dim3((unsigned)nb), dim3(FIG_SQ_NT), 0, ctx->stream, A);
+        FIG_HIP(hipGetLastError());
+        FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        FIG_HIP(P.fetch(out->wcount, dp, plane * sizeof(double)));
+        FIG_HIP(P.fetch(out->eloglik, dp + plane, plane * sizeof(double)));
+        FIG_HIP(P.fetch(hact.data(), dp + 2 * plane, nb * sizeof(int32_t)));
+        if (pl) FIG_HIP(PP.fetch(P));
+        FIG_HIP(hipStreamSynchronize(ctx->stream));
+        FIG_HIP(hipEventElapsedTime(&ms_place, ctx->ev0, mid.e));
+        FIG_HIP(hipEventElapsedTime(&ms_soft, mid.e, ctx->ev1));
+        for (int32_t a : hact) active += a;
+    }
+    if (pl) PP.finish(pl, ng, work);
+    for (int64_t g = 0; g < ng; g++)
+        if (out->state[g] == FIG_SOFTQ_ON)
+            for (int64_t i = f->str_off[g], e = f->str_off[g] + PP.ncol[(size_t)g]; i < e; i++) out->phred[i] = fig_quality_phred(out->eloglik + i * 4, f->str[i]);
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figsoftq] gaps on %lld of %lld, columns %lld, reads %lld, active placements %lld, placement kernel %.3f ms, softqual kernel %.3f ms\n",
+                (long long)PP.gaps_on, (long long)ng, (long long)PP.cols, (long long)PP.reads, (long long)active, ms_place, ms_soft);
     return FIG_OK;
 }
 

@@ -4,6 +4,7 @@
 #include "../fig_gaprules.h"
 #include "../fig_quality_host.h"
 #include "../fig_placement_host.h"
+#include "../fig_softqual_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -756,15 +757,19 @@ bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::stri
     });
 }
 
-bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+// the two Phred-per-base files: `n state` and n characters of Phred+33
+static bool write_phred_file(const RunArgs &a, const Batch &b, const Results &r, const char *name, const std::vector<uint8_t> &phred, const std::vector<uint8_t> &state, std::string &err) {
     std::string Q;
-    return write_per_gap(a, b, "gapquality.txt", err, [&](FILE *f, size_t g) {
+    return write_per_gap(a, b, name, err, [&](FILE *f, size_t g) {
         const int n = r.filled_len[g];
         Q.clear();
-        for (int x = 0; x < n; x++) Q += (char)(33 + r.qual_phred[(size_t)r.str_off[g] + x]);
-        fprintf(f, "%d\t%d\t%s\n", n, (int)r.qual_state[g], Q.c_str());
+        for (int x = 0; x < n; x++) Q += (char)(33 + phred[(size_t)r.str_off[g] + x]);
+        fprintf(f, "%d\t%d\t%s\n", n, (int)state[g], Q.c_str());
     });
 }
+
+bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) { return write_phred_file(a, b, r, "gapquality.txt", r.qual_phred, r.qual_state, err); }
+bool write_softquality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) { return write_phred_file(a, b, r, "gapsoftquality.txt", r.softq_phred, r.softq_state, err); }
 
 bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     std::string Q;
@@ -1147,4 +1152,32 @@ extern "C" int fighost_run_write_placement(void *h, const int32_t *filled_len, c
     R.place_state.assign(state, state + r->B.gap_contig.size());
     std::string e;
     return written(fighost::write_placement(r->a, r->B, R, e), e, err, errcap);
+}
+
+// ------------------------------------------------------------------ quality summed over placements (fig_softqual_host.h)
+// FIG_SOFTQ_* of `ng` gaps: the placement's rule
+extern "C" int fighost_softqual_gaps_on(int unmapped_model, int64_t ng, const int32_t *filled_len, const int32_t *draw_len, const int32_t *origin, uint8_t *state) {
+    for (int64_t g = 0; g < ng; g++) state[g] = fig_softqual_gap_on(unmapped_model != 0, filled_len[g], draw_len[2 * g], draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+    return 0;
+}
+
+// 1 iff a valid placement with d = Lr(o) - M_r is active
+extern "C" int fighost_softqual_active(double d) { return fig_softqual_active(d) ? 1 : 0; }
+
+// M, Z and "takes part" of `n` scored reads from the three doubles of the placement pass
+extern "C" int fighost_softqual_mz(int64_t n, const double *ll_drawn, const double *ll_other, const double *sum_other, double *M, double *Z, uint8_t *part) {
+    for (int64_t i = 0; i < n; i++) part[i] = fig_softqual_mz(ll_drawn[i], ll_other[i], sum_other[i], M[i], Z[i]) ? 1 : 0;
+    return 0;
+}
+
+// gapsoftquality.txt of the WHOLE gap set (FIGFILL_SOFTQUALITY=1): phred [str_off[n_gaps]] indexed like the strings, state [n_gaps]
+extern "C" int fighost_run_write_softquality(void *h, const int32_t *filled_len, const int64_t *str_off, const uint8_t *phred, const uint8_t *state,
+                                             char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size();
+    fighost::Results R = side_results(r, filled_len, str_off);
+    R.softq_phred.assign(phred, phred + (size_t)str_off[ng]);
+    R.softq_state.assign(state, state + ng);
+    std::string e;
+    return written(fighost::write_softquality(r->a, r->B, R, e), e, err, errcap);
 }

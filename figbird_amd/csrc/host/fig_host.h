@@ -92,6 +92,8 @@ struct Results {
     std::vector<uint8_t> qual_phred, qual_state;
     // placement confidence (fig_read_placement), when asked for: pq [unmapped reads] indexed like draw_pos, and FIG_PLACE_* [n_gaps]
     std::vector<uint8_t> place_pq, place_state;
+    // per-base quality summed over read placements (fig_gap_softqual), when asked for: Phred [str.size()] indexed like str, and FIG_SOFTQ_* [n_gaps]
+    std::vector<uint8_t> softq_phred, softq_state;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
@@ -103,6 +105,8 @@ bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::stri
 // gapquality.txt (no counterpart in the reference): per gap `g contig start G0 n state Q`, tab-separated, the first five fields
 // as in gapout.txt, state = FIG_QUAL_*, Q = n characters of Phred+33 (empty for n <= 0)
 bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gapsoftquality.txt (no counterpart in the reference): gapquality.txt's format, state = FIG_SOFTQ_*, Q from fig_gap_softqual::phred
+bool write_softquality(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // gapplacement.txt (no counterpart in the reference): per gap `g contig start G0 n state R Q`, tab-separated, the first five fields
 // as in gapout.txt, state = FIG_PLACE_*, R = the gap's unmapped read count, Q = R characters: Phred+33 of the read's pq, or '~'
 // for a read that was not scored

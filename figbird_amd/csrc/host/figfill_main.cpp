@@ -19,28 +19,30 @@
 
 using namespace fighost;
 
-// Three calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
+// Four calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
 // written against): bound weakly, and asking for what they compute without them is an error before anything is filled or written.
 extern "C" int fig_fill_resident_ex(fig_ctx *, fig_gap_results *, const fig_gap_support *) __attribute__((weak));
 extern "C" int fig_batch_quality(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_quality *) __attribute__((weak));
 extern "C" int fig_batch_placement(fig_ctx *, const fig_gap_results *, const int32_t *, fig_read_placement *) __attribute__((weak));
+extern "C" int fig_batch_softqual(fig_ctx *, const fig_gap_results *, const int32_t *, fig_read_placement *, fig_gap_softqual *) __attribute__((weak));
 
 // The optional outputs: read from the environment once, in main(), and passed down.
 //   FIGFILL_SUPPORT=1    also the per-base read support and <tmp>/gapsupport.txt
 //   FIGFILL_QUALITY=1    the fill with the support call (for the origins), then fig_batch_quality, and <tmp>/gapquality.txt
 //   FIGFILL_PLACEMENT=1  the fill with the support call, then fig_batch_placement, and <tmp>/gapplacement.txt
+//   FIGFILL_SOFTQUALITY=1  the fill with the support call, then fig_batch_softqual, and <tmp>/gapsoftquality.txt
 //   FIGFILL_QUALITY_MINPQ=<k> (only together with FIGFILL_QUALITY=1): the quality leaves out scored reads with pq < k
 struct Wants {
-    bool support_file = false, quality = false, placement_file = false;
+    bool support_file = false, quality = false, placement_file = false, softquality = false;
     int min_pq = -1;                                                            // -1 = not set
     bool placement() const { return placement_file || min_pq >= 0; }            // the call is needed for the file and for the filter
-    bool support() const { return support_file || quality || placement(); }
+    bool support() const { return support_file || quality || placement() || softquality; }
 };
 
 static Wants wants_from_env() {
     auto is1 = [](const char *name) { const char *s = getenv(name); return s && atoi(s) == 1; };
     Wants w;
-    w.support_file = is1("FIGFILL_SUPPORT"); w.quality = is1("FIGFILL_QUALITY"); w.placement_file = is1("FIGFILL_PLACEMENT");
+    w.support_file = is1("FIGFILL_SUPPORT"); w.quality = is1("FIGFILL_QUALITY"); w.placement_file = is1("FIGFILL_PLACEMENT"); w.softquality = is1("FIGFILL_SOFTQUALITY");
     const char *s = getenv("FIGFILL_QUALITY_MINPQ");
     w.min_pq = s && *s && w.quality ? atoi(s) : -1;
     return w;
@@ -71,6 +73,14 @@ static int quality_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R,
     return fig_batch_quality(ctx, &f2, R.sup_origin.data(), &gq);
 }
 
+// the quality summed over placements of the fill `fr` just returned (the batch still resident): R.softq_phred / R.softq_state
+static int softquality_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng) {
+    R.softq_phred.assign((size_t)std::max<int64_t>(fr->str_capacity, 1), 0); R.softq_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<double> pl((size_t)std::max<int64_t>(fr->str_off[ng], 1) * 8, 0.0);
+    fig_gap_softqual sq; sq.wcount = pl.data(); sq.eloglik = pl.data() + pl.size() / 2; sq.phred = R.softq_phred.data(); sq.state = R.softq_state.data();
+    return fig_batch_softqual(ctx, fr, R.sup_origin.data(), nullptr, &sq);
+}
+
 // The fill of the batch `fb` (nu unmapped + np partial reads) resident in ctx, as both the single-device path and a shard run it:
 // R is sized, `fr` -- zeroed by the caller, who may have set its dbg_* fields -- becomes the view of R the library fills, then
 // the fill (with R.sup_counts / R.sup_origin when `w` needs the support call) and the passes beside it that `w` asks for.
@@ -96,13 +106,15 @@ static int fill_batch(fig_ctx *ctx, const fig_model *fm, const fig_gap_batch *fb
     fig_get_stats(ctx, st);
     if (!rc && w.placement()) { what = "fig_batch_placement"; rc = placement_resident(ctx, &fr, R, ng, nu); }
     if (!rc && w.quality) { what = "fig_batch_quality"; rc = quality_resident(ctx, &fr, R, ng, nu, w.min_pq); }
+    if (!rc && w.softquality) { what = "fig_batch_softqual"; rc = softquality_resident(ctx, &fr, R, ng); }
     return rc;
 }
 
 // every file of a run
 static bool write_outputs(const RunArgs &a, const Scaffold &sc, const Batch &B, const Results &R, const Wants &w, std::string &err) {
     return write_gapout(a, B, R, err) && write_draw(a, B, R, err) && write_gaploads(a, B, err) && write_scaffold(a, sc, B, R, err) &&
-           (!w.support_file || write_support(a, B, R, err)) && (!w.quality || write_quality(a, B, R, err)) && (!w.placement_file || write_placement(a, B, R, err));
+           (!w.support_file || write_support(a, B, R, err)) && (!w.quality || write_quality(a, B, R, err)) && (!w.placement_file || write_placement(a, B, R, err)) &&
+           (!w.softquality || write_softquality(a, B, R, err));
 }
 
 static int fail(const std::string &m) { fprintf(stderr, "%s\n", m.c_str()); return 1; }
@@ -189,6 +201,7 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
     if (support) R.sup_origin.assign((size_t)std::max<int64_t>(ng, 1), 0);
     if (placement) { R.place_pq.assign((size_t)std::max<int64_t>(NU, 1), FIG_PLACE_NONE); R.place_state.assign((size_t)std::max<int64_t>(ng, 1), 0); }
     if (quality) R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    if (w.softquality) R.softq_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
     for (int64_t g = 0; g < ng; g++) {
         const ShardRun &S = runs[owner[g]]; const int64_t k = local[g];
         R.filled_len[g] = S.R.filled_len[k]; R.gaptofill[g] = S.R.gaptofill[k];
@@ -201,6 +214,10 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         if (quality) {                                    // and so does the Phred: one byte per string byte
             R.qual_phred.insert(R.qual_phred.end(), S.R.qual_phred.begin() + S.R.str_off[k], S.R.qual_phred.begin() + S.R.str_off[k + 1]);
             R.qual_state[g] = S.R.qual_state[k];
+        }
+        if (w.softquality) {
+            R.softq_phred.insert(R.softq_phred.end(), S.R.softq_phred.begin() + S.R.str_off[k], S.R.softq_phred.begin() + S.R.str_off[k + 1]);
+            R.softq_state[g] = S.R.softq_state[k];
         }
         R.draw_len[2 * g] = S.R.draw_len[2 * k]; R.draw_len[2 * g + 1] = S.R.draw_len[2 * k + 1];
         const int64_t nu = B.u_read_off[g + 1] - B.u_read_off[g], np = B.p_read_off[g + 1] - B.p_read_off[g];
@@ -216,6 +233,7 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
     if (R.str.empty()) R.str.assign(1, 'N');
     if (support && R.sup_counts.empty()) R.sup_counts.assign(5, 0);
     if (quality && R.qual_phred.empty()) R.qual_phred.assign(1, 0);
+    if (w.softquality && R.softq_phred.empty()) R.softq_phred.assign(1, 0);
     return 0;
 }
 
@@ -249,6 +267,7 @@ int main(int argc, char **argv) {
     const Wants w = wants_from_env();
     if (w.placement() && !fig_batch_placement)
         return fail("figfill: FIGFILL_PLACEMENT=1 and FIGFILL_QUALITY_MINPQ need fig_batch_placement, which the library behind this build does not export");
+    if (w.softquality && !fig_batch_softqual) return fail("figfill: FIGFILL_SOFTQUALITY=1 needs fig_batch_softqual, which the library behind this build does not export");
     if (w.quality && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
     setenv("GPU_MAX_HW_QUEUES", "8", 0);                 // one hardware queue per scheduler lane; before any thread or HIP call (fig_abi.hip: fig_ctx_create)
     auto t0 = std::chrono::steady_clock::now();

@@ -237,6 +237,45 @@ typedef struct fig_read_placement {
     uint8_t *state;      /* [n_gaps] FIG_PLACE_* */
 } fig_read_placement;
 
+/* Optional per-base quality that sums over read placements (fig_batch_softqual).  fig_gap_quality takes the placement of every
+ * read as given: a read that fits three offsets equally well is piled up at full weight on the first of them.  Here a scored read
+ * counts on every placement by the share of it that could be there.  Every term not redefined below means what it means for
+ * fig_gap_quality and fig_read_placement: the sequence S(x) of a gap, the placements o in [-(len-1), n-1], isz(o) and the validity
+ * rule, the score Lr(o) with li, lm, le, lt, lq, the index k, the skipping of read bases outside ACGT, and which reads are scored.
+ *
+ * Gaps.  A gap is FIG_SOFTQ_ON iff it is FIG_PLACE_ON; every other gap is FIG_SOFTQ_OFF: its planes are all 0.0 and its Phred all
+ * 0, written by the library whatever the buffers held.
+ *
+ * Weights of a scored read r.  M_r = the greatest Lr(o) over its valid placements, the drawn one included when it is valid.  A read
+ * with no valid placement, or with M_r = -inf, takes no part.  Otherwise d(o) = Lr(o) - M_r (one IEEE subtraction); a valid
+ * placement is ACTIVE iff d(o) >= -300 (an exact comparison of exactly reproducible doubles, which keeps -inf and underflow out of
+ * what follows); u(o) = 10^d(o); Z_r = the sum of u over the active placements; p_r(o) = u(o) / Z_r.  The library takes Z_r from the
+ * placement pass as sum_other + 10^(ll_drawn - M_r): the terms below the cut change it by less than 1e-297 relative.
+ *
+ * Planes, per column 0 <= x < n of a gap that is on.  The sums run over the scored reads r and their active placements o with
+ * j = x - o in [0, len) and base j of the read one of ACGT: s its code, k its table index.
+ *   wcount[x][s]   the sum of p_r(o): the expected number of reads that show s on the column (the soft form of the support counts)
+ *   eloglik[x][b]  the sum of p_r(o) * t, t = lm[k] if s == b, else le[k] + lt[b][s]: the expected log10-likelihood of true base b
+ * A -inf term with an active weight makes the entry -inf.  A column with no contribution is exactly 0.0.  Every term of an entry has
+ * one sign; the device adds them read by read in ascending read index and, within a read, in ascending j.
+ *
+ * phred[x] = the Phred of fig_gap_quality applied to eloglik[x] and the emitted byte.
+ *
+ * When every read has exactly one active placement and it is the drawn one, p = 1: eloglik is fig_gap_quality's loglik and wcount
+ * the A..T columns of the support counts (their fifth, "other" column has no counterpart here).
+ *
+ * Limits of the number: the score of a placement includes the read's own base on column x against the emitted call (the E-step's
+ * circularity); reads are taken as independent; substitutions only; a uniform prior over the bases of an N column; undrawn reads
+ * and partial reads take no part. */
+#define FIG_SOFTQ_OFF 0
+#define FIG_SOFTQ_ON  1
+typedef struct fig_gap_softqual {
+    double  *wcount;   /* [str_off[n_gaps]*4]  (str_off[g]+x)*4 + s */
+    double  *eloglik;  /* [str_off[n_gaps]*4]  (str_off[g]+x)*4 + b */
+    uint8_t *phred;    /* [str_off[n_gaps]] */
+    uint8_t *state;    /* [n_gaps] FIG_SOFTQ_* */
+} fig_gap_softqual;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -296,6 +335,15 @@ int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *filled, const int32_t
  * offset |o| >= 2^20 in a gap that is on.  With FIG_SCHED_LOG set, one "[figplace]" line on stderr: gaps on, reads scored,
  * placements scored, HIP-event milliseconds of the kernel. */
 int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, fig_read_placement *p);
+
+/* Per-base quality summed over read placements, of `filled` against the RESIDENT batch (see fig_gap_softqual); `filled` and origin as
+ * for fig_batch_placement, and the same FIG_EINVAL conditions (a NULL member of `out`, or of `placement_or_null` when that is given,
+ * included).  Two launches on the library's stream with no host round trip between them: the placement pass into per-call buffers,
+ * then the pass that reads them.  placement_or_null, when given, is filled exactly as fig_batch_placement fills it: one call yields
+ * both.  Reads the resident batch and the model and writes neither.  With FIG_SCHED_LOG set, one "[figsoftq]" line on stderr: gaps
+ * on, columns, reads, active placements, HIP-event milliseconds of each of the two launches. */
+int fig_batch_softqual(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin,
+                       fig_read_placement *placement_or_null, fig_gap_softqual *out);
 
 int fig_get_stats(const fig_ctx *ctx, fig_stats *out);
 
