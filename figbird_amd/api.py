@@ -114,6 +114,35 @@ class SoftQual:
     placement: Optional[Placement] = None
 
 
+class FigGapIndel(C.Structure):
+    _fields_ = [("ll_flat", c_double_p), ("ll_gapped", c_double_p), ("n_ins", c_i32_p), ("n_del", c_i32_p), ("d_end", c_i32_p), ("d_start", c_i32_p),
+                ("del_reads", c_i32_p), ("ins_reads", c_i32_p), ("cover", c_i32_p), ("ins_end", c_i32_p),
+                ("call", c_u8_p), ("call_end", c_u8_p), ("state", c_u8_p)]
+
+
+# fig_gap_indel::state and the band's half width (include/figbird_hip.h)
+INDEL_OFF, INDEL_ON, INDEL_W = 0, 1, 7
+
+
+@dataclass
+class Indel:
+    """fig_gap_indel of one call: the six per-read arrays are indexed like the unmapped part of draw_pos, the three planes and call
+    (uint8: ord of 'D', 'I' or '.') like the strings (base x of gap g at str_off[g] + x), ins_end, call_end and state per gap"""
+    ll_flat: np.ndarray
+    ll_gapped: np.ndarray
+    n_ins: np.ndarray
+    n_del: np.ndarray
+    d_end: np.ndarray
+    d_start: np.ndarray
+    del_reads: np.ndarray
+    ins_reads: np.ndarray
+    cover: np.ndarray
+    ins_end: np.ndarray
+    call: np.ndarray
+    call_end: np.ndarray
+    state: np.ndarray
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -124,7 +153,7 @@ class FigStats(C.Structure):
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
            "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
            "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality", "fig_batch_placement",
-           "fig_batch_softqual"]
+           "fig_batch_softqual", "fig_batch_indel"]
 
 _lib = None
 _host = None
@@ -164,6 +193,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.fig_batch_placement.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigReadPlacement)]
     if hasattr(lib, "fig_batch_softqual"):            # (likewise)
         lib.fig_batch_softqual.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigReadPlacement), C.POINTER(FigGapSoftqual)]
+    if hasattr(lib, "fig_batch_indel"):               # (likewise)
+        lib.fig_batch_indel.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigGapIndel)]
     if path is None:
         _lib = lib
     return lib
@@ -203,6 +234,13 @@ def load_host_library() -> C.CDLL:
         _host.fighost_softqual_active.argtypes = [C.c_double]
         _host.fighost_softqual_mz.argtypes = [C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_u8_p]
         _host.fighost_run_write_softquality.argtypes = [C.c_void_p, c_i32_p, c_i64_p, c_u8_p, c_u8_p, C.c_char_p, C.c_int]
+        _host.fighost_indel_tables.argtypes = [C.POINTER(FigModel), c_double_p, c_double_p]
+        _host.fighost_indel_gaps_on.argtypes = [C.c_int, C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
+        _host.fighost_indel_aligned.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        _host.fighost_indel_end_order.argtypes = [C.c_int]
+        _host.fighost_indel_call.argtypes = [C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
+        _host.fighost_indel_call_end.argtypes = [C.c_int32, C.c_int32]
+        _host.fighost_run_write_indel.argtypes = [C.c_void_p, c_i32_p, c_i64_p, C.c_char_p, C.c_char_p, c_u8_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -349,6 +387,7 @@ class FillResult:
     support_origin: Optional[np.ndarray] = None   # int32 [n_gaps]: SUP_* mask (fig_gap_support::origin)
     placement: Optional["Placement"] = None   # fig_read_placement of the fill's drawn unmapped reads, when requested
     quality: Optional[tuple] = None        # (loglik float64 [total, 4], phred uint8 [total], state uint8 [n_gaps]) of fig_gap_quality, indexed like raw
+    indel: Optional["Indel"] = None        # fig_gap_indel of the fill's strings and drawn unmapped reads, when requested
     softqual: Optional["SoftQual"] = None  # fig_gap_softqual of the fill's strings, when requested
 
     @property
@@ -490,6 +529,33 @@ class Engine:
         self._check(self.lib.fig_batch_softqual(self.ctx, C.byref(r), org_p, C.byref(rp) if placement else None, C.byref(sq)), "fig_batch_softqual")
         return SoftQual(wc[:total], el[:total], ph[:total], stt[:n], plc)
 
+    def indel(self, res: FillResult, origin: Optional[np.ndarray] = None) -> "Indel":
+        """fig_batch_indel of the strings and draw planes in `res` against the resident batch; `origin` as for quality().  The buffers
+        handed to the library start as 0xFF bytes, so that an element it failed to write shows."""
+        self._need("fig_batch_indel", "indel")
+        r, keep = self._filled_struct("indel", res)
+        n, nu = self.n_gaps, self._n_ureads()
+        if len(keep[3]) < nu:
+            raise ValueError("indel: one drawn offset per unmapped read of the resident batch")
+        total = int(keep[1][n])
+        org, org_p = self._origin_arg("indel", origin)
+        m, t, gm = max(nu, 1), max(total, 1), max(n, 1)
+        d = [np.zeros(m) for _ in range(2)]
+        for a in d:
+            a.view(np.uint8)[...] = 0xFF
+        ri = [np.full(m, -1, dtype=np.int32) for _ in range(4)]
+        pl = [np.full(t, -1, dtype=np.int32) for _ in range(3)]
+        ie = np.full(gm, -1, dtype=np.int32)
+        call = np.full(t, 0xFF, dtype=np.uint8); ce = np.full(gm, 0xFF, dtype=np.uint8); stt = np.full(gm, 0xFF, dtype=np.uint8)
+        gi = FigGapIndel()
+        gi.ll_flat = _p(d[0], c_double_p); gi.ll_gapped = _p(d[1], c_double_p)
+        gi.n_ins, gi.n_del, gi.d_end, gi.d_start = (_p(a, c_i32_p) for a in ri)
+        gi.del_reads, gi.ins_reads, gi.cover = (_p(a, c_i32_p) for a in pl)
+        gi.ins_end = _p(ie, c_i32_p); gi.call = _p(call, c_u8_p); gi.call_end = _p(ce, c_u8_p); gi.state = _p(stt, c_u8_p)
+        self._check(self.lib.fig_batch_indel(self.ctx, C.byref(r), org_p, C.byref(gi)), "fig_batch_indel")
+        return Indel(d[0][:nu], d[1][:nu], ri[0][:nu], ri[1][:nu], ri[2][:nu], ri[3][:nu], pl[0][:total], pl[1][:total], pl[2][:total], ie[:n],
+                     call[:total], ce[:n], stt[:n])
+
     def quality(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: Optional["Placement"] = None, min_pq: Optional[int] = None):
         """fig_batch_quality of the strings and draw planes in `res` against the resident batch; `origin` is
         FillResult.support_origin, or None for no origin test.  Returns (loglik [total, 4], phred [total], state [n_gaps]) with
@@ -515,15 +581,17 @@ class Engine:
         self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), org_p, C.byref(gq)), "fig_batch_quality")
         return ll[:total], ph[:total], stt[:n]
 
-    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False):
-        """quality, placement and softqual need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False, indel: bool = False):
+        """quality, placement, softqual and indel need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
         if quality:
             self._need("fig_batch_quality", "quality=True")
         if placement:
             self._need("fig_batch_placement", "placement=True")
         if softqual:
             self._need("fig_batch_softqual", "softqual=True")
-        return draw or quality or placement or softqual, support or quality or placement or softqual
+        if indel:
+            self._need("fig_batch_indel", "indel=True")
+        return draw or quality or placement or softqual or indel, support or quality or placement or softqual or indel
 
     def _result_arrays(self, n: int, cap: int, nr: Optional[int], draw: bool):
         """Fresh result arrays for n gaps and cap string bytes and, unless nr is None, draw planes for nr reads, behind a
@@ -540,20 +608,21 @@ class Engine:
             r.draw_pos = _p(planes[0], c_i32_p); r.draw_isz = _p(planes[1], c_i32_p); r.draw_len = _p(planes[2], c_i32_p)
         return r, fl, gt, so, st, planes
 
-    def _post_fill(self, filled: FillResult, placement: bool, quality: bool, min_pq: Optional[int] = None, softqual: bool = False):
-        """the passes beside a fill whose batch is still resident, with its origins -> (Placement or None, quality or None, SoftQual or None)"""
+    def _post_fill(self, filled: FillResult, placement: bool, quality: bool, min_pq: Optional[int] = None, softqual: bool = False, indel: bool = False):
+        """the passes beside a fill whose batch is still resident, with its origins -> (Placement or None, quality or None, SoftQual or
+        None, Indel or None)"""
         plc = self.placement(filled, filled.support_origin) if placement else None
         qual = None
         if quality:
             qual = self.quality(filled, filled.support_origin, placement=plc if min_pq is not None else None, min_pq=min_pq)
-        return plc, qual, (self.softqual(filled, filled.support_origin) if softqual else None)
+        return plc, qual, (self.softqual(filled, filled.support_origin) if softqual else None), (self.indel(filled, filled.support_origin) if indel else None)
 
     def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-                      placement: bool = False, softqual: bool = False) -> FillResult:
+                      placement: bool = False, softqual: bool = False, indel: bool = False) -> FillResult:
         """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins);
         placement=True likewise fills FillResult.placement (fig_batch_placement with the origins), softqual=True
-        FillResult.softqual (fig_batch_softqual with the origins)."""
-        draw, support = self._implied(support, draw, quality, placement, softqual)
+        FillResult.softqual (fig_batch_softqual with the origins), indel=True FillResult.indel (fig_batch_indel with the origins)."""
+        draw, support = self._implied(support, draw, quality, placement, softqual, indel)
         n = self.n_gaps
         nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1]) if draw else None
         r, fl, gt, so, st, planes = self._result_arrays(n, self.cap, nr, draw)
@@ -588,7 +657,7 @@ class Engine:
             res.draw = (planes[0][:nr], planes[1][:nr], planes[2][:2 * n])
         if support:
             res.support = sup_c[:int(so[n])]; res.support_origin = sup_o[:n]
-        res.placement, res.quality, res.softqual = self._post_fill(res, placement, quality, softqual=softqual)
+        res.placement, res.quality, res.softqual, res.indel = self._post_fill(res, placement, quality, softqual=softqual, indel=indel)
         return res
 
     def free_batch(self):
@@ -618,7 +687,7 @@ class Engine:
             self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
 
     def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False, quality: bool = False,
-                    keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None, softqual: bool = False) -> FillResult:
+                    keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None, softqual: bool = False, indel: bool = False) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
         resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
@@ -626,10 +695,10 @@ class Engine:
         fig_batch_quality before the batch is freed (field `quality`).  keep_resident=True leaves an uploaded batch resident
         for a further call.  placement=True likewise runs fig_batch_placement (field `placement`); with min_pq as well the
         quality leaves out the scored reads below that pq (Engine.quality).  softqual=True likewise runs fig_batch_softqual (field
-        `softqual`)."""
-        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual)
+        `softqual`), indel=True fig_batch_indel (field `indel`)."""
+        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual, indel)
         placement = placement or min_pq is not None
-        qual = plc = sq = None
+        qual = plc = sq = ind = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         nr = n_ureads + n_preads
@@ -643,9 +712,9 @@ class Engine:
         if n > 0 and resident:
             try:
                 sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
-                if placement or quality or softqual:
+                if placement or quality or softqual or indel:
                     self.n_gaps = n; self._cb = cbatch
-                    plc, qual, sq = self._post_fill(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), placement, quality, min_pq, softqual)
+                    plc, qual, sq, ind = self._post_fill(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), placement, quality, min_pq, softqual, indel)
             finally:
                 if not keep_resident:
                     self.lib.fig_batch_free(self.ctx)
@@ -663,13 +732,16 @@ class Engine:
             res.placement = plc if plc is not None else Placement(z, z, z, np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
         if softqual:
             res.softqual = sq if sq is not None else SoftQual(np.zeros((0, 4)), np.zeros((0, 4)), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
+        if indel:
+            zi, zb = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8)
+            res.indel = ind if ind is not None else Indel(np.zeros(0), np.zeros(0), zi, zi, zi, zi, zi, zi, zi, zi, zb, zb, zb)
         return res
 
     def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-             placement: bool = False, softqual: bool = False) -> FillResult:
+             placement: bool = False, softqual: bool = False, indel: bool = False) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual, indel)
         finally:
             self.free_batch()
 

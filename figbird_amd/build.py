@@ -22,6 +22,8 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # -ffp-contract=off: the reference multiplies and adds separately (no FMA on its x86-64 build);
 # bit-identical pile-up weights need the same two roundings.
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wno-unused-value"]
+# the translation units of libfighip.so: the engine with its ABI, and the indel kernel in a module of its own (fig_indel.h)
+LIB_SOURCES = [os.path.join(CSRC, "fig_abi.hip"), os.path.join(CSRC, "fig_indel_kernel.hip")]
 
 
 def _csrc_files():
@@ -50,7 +52,7 @@ def build_lib(force: bool = False) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     srcs = _csrc_files()
     if force or not _newer(LIB, srcs):
-        _run([HIPCC] + HIP_FLAGS + ["-o", LIB, os.path.join(CSRC, "fig_abi.hip")])
+        _run([HIPCC] + HIP_FLAGS + ["-o", LIB] + LIB_SOURCES)
     return LIB
 
 
@@ -59,7 +61,7 @@ def build_prof_lib() -> str:
     default (tools/gpu_probe.py takes it through FIG_LIB)."""
     out = os.path.join(LIBDIR, "libfighip_prof.so")
     if not _newer(out, _csrc_files()):
-        _run([HIPCC] + HIP_FLAGS + ["-DFIG_PROF", "-o", out, os.path.join(CSRC, "fig_abi.hip")])
+        _run([HIPCC] + HIP_FLAGS + ["-DFIG_PROF", "-o", out] + LIB_SOURCES)
     return out
 
 
@@ -77,7 +79,7 @@ def build_figfill(force: bool = False) -> str:
     main_cpp = os.path.join(host, "figfill_main.cpp")
     srcs = hdrs + libs + [main_cpp, os.path.join(ROOT, "include", "figbird_hip.h"), os.path.join(CSRC, "fig_gaprules.h"),
                           os.path.join(CSRC, "fig_quality_host.h"), os.path.join(CSRC, "fig_placement_host.h"),
-                          os.path.join(CSRC, "fig_softqual_host.h")]      # (figtool_main.cpp is built below)
+                          os.path.join(CSRC, "fig_softqual_host.h"), os.path.join(CSRC, "fig_indel_host.h")]      # (figtool_main.cpp is built below)
     common = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread"]
     if force or not _newer(FIGFILL, srcs + [LIB]):
         _run(common + ["-o", FIGFILL, main_cpp] + libs + ["-L" + LIBDIR, "-lfighip", "-Wl,-rpath,$ORIGIN/../lib"])

@@ -24,6 +24,7 @@
 #include "fig_quality_host.h"
 #include "fig_placement.h"
 #include "fig_softqual.h"
+#include "fig_indel.h"
 
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
@@ -317,6 +318,7 @@ struct fig_ctx {
     FigDevModel dm;
     DevBuf d_model_tabs;
     fig_model hm;
+    std::vector<double> h_ins, h_del; // in_pos_dist / del_pos_dist of the model (hm's pointers are the caller's and need not outlive the call)
     // resident batch
     bool have_batch = false;
     FigDevBatch db;
@@ -424,6 +426,8 @@ extern "C" int fig_ctx_set_model(fig_ctx *ctx, const fig_model *m) {
     hipSetDevice(ctx->device);
     free_batch(ctx);                  // a resident batch was packed (classes, capacities, candidate ranges) under the previous model
     ctx->hm = *m;
+    ctx->h_ins.assign(m->in_pos_dist, m->in_pos_dist + m->max_read_length);
+    ctx->h_del.assign(m->del_pos_dist, m->del_pos_dist + m->max_read_length);
     std::vector<double> all;
     FigModelOffsets o;
     fig_model_tables(m, all, o, ctx->dm);
@@ -1021,6 +1025,91 @@ extern "C" int fig_batch_softqual(fig_ctx *ctx, const fig_gap_results *f, const 
     if (fig_knobs_from_env(ctx->dm.unmapped).log)
         fprintf(stderr, "[figsoftq] gaps on %lld of %lld, columns %lld, reads %lld, active placements %lld, placement kernel %.3f ms, softqual kernel %.3f ms\n",
                 (long long)PP.gaps_on, (long long)ng, (long long)PP.cols, (long long)PP.reads, (long long)active, ms_place, ms_soft);
+    return FIG_OK;
+}
+
+// Indel evidence per filled base (fig_indel.h: the kernel and the path; fig_indel_host.h: tables, which gaps are on, which reads are
+// aligned, the call)
+extern "C" int fig_batch_indel(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_indel *out) {
+    if (!out || !out->ll_flat || !out->ll_gapped || !out->n_ins || !out->n_del || !out->d_end || !out->d_start || !out->del_reads || !out->ins_reads ||
+        !out->cover || !out->ins_end || !out->call || !out->call_end || !out->state) return FIG_EINVAL;
+    FigPostFill P;
+    FIG_TRY(P.open(ctx, f));
+    const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
+    const FigDevBatch &db = ctx->db;
+    const int L = ctx->dm.L;
+    std::vector<int32_t> hlen((size_t)std::max<int64_t>(nu, 1), 0);
+    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+    // which gaps are on, which of their reads are aligned, and the bounds of what the kernel will index with
+    std::vector<int32_t> items, ncol((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<uint8_t> aligned((size_t)std::max<int64_t>(nu, 1), 0);
+    int64_t gaps_on = 0, reads = 0, events = 0, called = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        const int32_t n = f->filled_len[g];
+        out->state[g] = fig_indel_gap_on(ctx->dm.unmapped != 0, n, f->draw_len[2 * g], f->draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+        if (out->state[g] != FIG_INDEL_ON) continue;
+        const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
+        if (P.drawn_reads(g, n, base, cnt, nu) < 0) return FIG_EINVAL;
+        gaps_on++; ncol[(size_t)g] = n;
+        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {                  // a chunk without an aligned read is no work item
+            bool any = false;
+            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) {
+                const bool a = fig_indel_aligned(f->draw_pos[base + r], std::min(std::max(hlen[(size_t)(base + r)], 0), L), n);
+                aligned[(size_t)(base + r)] = a; any = any || a; reads += a;
+            }
+            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
+        }
+    }
+    for (int64_t r = 0; r < nu; r++) { out->ll_flat[r] = 0.0; out->ll_gapped[r] = 0.0; out->n_ins[r] = 0; out->n_del[r] = 0; out->d_end[r] = 0; out->d_start[r] = INT32_MIN; }
+    for (int64_t i = 0; i < total; i++) { out->del_reads[i] = 0; out->ins_reads[i] = 0; out->cover[i] = 0; out->call[i] = '.'; }
+    for (int64_t g = 0; g < ng; g++) { out->ins_end[g] = 0; out->call_end[g] = '.'; }
+    if (!items.empty()) {
+        std::vector<double> tid((size_t)(2 * L));
+        fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
+        FigIndelArgs A;
+        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank; A.L = L;
+        A.draw_pos = P.up(f->draw_pos, (size_t)nu);
+        A.items = P.up(items.data(), items.size());
+        A.ncol = P.up(ncol.data(), (size_t)ng);
+        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
+        A.str = P.up(f->str, (size_t)total);
+        A.tabs = P.up(P.tabs.data(), P.tabs.size());
+        A.tabs_id = P.up(tid.data(), tid.size());
+        double *dd = (double *)P.alloc((size_t)nu * 2 * sizeof(double));
+        int32_t *di = (int32_t *)P.alloc((size_t)nu * 4 * sizeof(int32_t));
+        const size_t ncnt = (size_t)total * 3 + (size_t)ng;                   // del_reads | ins_reads | cover | ins_end
+        int32_t *dc = (int32_t *)P.alloc(ncnt * sizeof(int32_t));
+        A.ll_flat = dd; A.ll_gapped = dd + nu; A.n_ins = di; A.n_del = di + nu; A.d_end = di + 2 * nu; A.d_start = di + 3 * nu;
+        A.del_reads = dc; A.ins_reads = dc + total; A.cover = dc + 2 * total; A.ins_end = dc + 3 * total;
+        if (dc) FIG_HIP(hipMemsetAsync(dc, 0, ncnt * sizeof(int32_t), ctx->stream));
+        std::vector<double> hd((size_t)nu * 2);
+        std::vector<int32_t> hi((size_t)nu * 4);
+        FIG_TRY(P.run([&] { fig_indel_launch(A, (unsigned)(items.size() / 2), ctx->stream); },
+                      [&] {
+                          hipError_t e = P.fetch(hd.data(), dd, hd.size() * sizeof(double));
+                          if (e == hipSuccess) e = P.fetch(hi.data(), di, hi.size() * sizeof(int32_t));
+                          if (e == hipSuccess && total > 0) e = P.fetch(out->del_reads, A.del_reads, (size_t)total * sizeof(int32_t));
+                          if (e == hipSuccess && total > 0) e = P.fetch(out->ins_reads, A.ins_reads, (size_t)total * sizeof(int32_t));
+                          if (e == hipSuccess && total > 0) e = P.fetch(out->cover, A.cover, (size_t)total * sizeof(int32_t));
+                          return e != hipSuccess ? e : P.fetch(out->ins_end, A.ins_end, (size_t)ng * sizeof(int32_t));
+                      }));
+        for (int64_t r = 0; r < nu; r++) {
+            if (!aligned[(size_t)r]) continue;
+            out->ll_flat[r] = hd[(size_t)r]; out->ll_gapped[r] = hd[(size_t)(nu + r)];
+            out->n_ins[r] = hi[(size_t)r]; out->n_del[r] = hi[(size_t)(nu + r)]; out->d_end[r] = hi[(size_t)(2 * nu + r)]; out->d_start[r] = hi[(size_t)(3 * nu + r)];
+            events += out->n_ins[r] + out->n_del[r] > 0;
+        }
+        for (int64_t g = 0; g < ng; g++) {
+            if (out->state[g] != FIG_INDEL_ON) continue;
+            const int64_t s0 = f->str_off[g], n = ncol[(size_t)g];
+            for (int64_t i = s0; i < s0 + n; i++) { out->call[i] = fig_indel_call(out->del_reads[i], out->ins_reads[i], out->cover[i]); called += out->call[i] != '.'; }
+            out->call_end[g] = fig_indel_majority(out->ins_end[g], out->cover[s0 + n - 1]) ? 'I' : '.';
+            called += out->call_end[g] != '.';
+        }
+    }
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figindel] gaps on %lld of %lld, reads aligned %lld, reads with an event %lld, columns called %lld, kernel %.3f ms\n",
+                (long long)gaps_on, (long long)ng, (long long)reads, (long long)events, (long long)called, P.ms);
     return FIG_OK;
 }
 

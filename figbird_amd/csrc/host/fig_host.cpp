@@ -5,6 +5,7 @@
 #include "../fig_quality_host.h"
 #include "../fig_placement_host.h"
 #include "../fig_softqual_host.h"
+#include "../fig_indel_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -781,6 +782,15 @@ bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::st
     });
 }
 
+bool write_indel(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+    return write_per_gap(a, b, "gapindel.txt", err, [&](FILE *f, size_t g) {
+        const int n = r.filled_len[g];
+        fprintf(f, "%d\t%d\t", n, (int)r.indel_state[g]);
+        if (n > 0) fwrite(r.indel_call.data() + r.str_off[g], 1, (size_t)n, f);
+        fprintf(f, "\t%c\n", r.indel_call_end[g]);
+    });
+}
+
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     FILE *f = fopen((a.tmp + "draw.txt").c_str(), "w");
     if (!f) { err = "can't write draw.txt"; return false; }
@@ -1180,4 +1190,42 @@ extern "C" int fighost_run_write_softquality(void *h, const int32_t *filled_len,
     R.softq_state.assign(state, state + ng);
     std::string e;
     return written(fighost::write_softquality(r->a, r->B, R, e), e, err, errcap);
+}
+
+// ------------------------------------------------------------------ indel evidence (fig_indel_host.h)
+// lI[L], lD[L] of the model, as fig_batch_indel builds them
+extern "C" int fighost_indel_tables(const fig_model *m, double *lI, double *lD) {
+    if (!m || !m->in_pos_dist || !m->del_pos_dist || !lI || !lD || m->max_read_length <= 0) return -1;
+    fig_indel_tables(m->max_read_length, m->in_pos_dist, m->del_pos_dist, lI, lD);
+    return 0;
+}
+
+// FIG_INDEL_* of `ng` gaps: the placement's rule
+extern "C" int fighost_indel_gaps_on(int unmapped_model, int64_t ng, const int32_t *filled_len, const int32_t *draw_len, const int32_t *origin, uint8_t *state) {
+    for (int64_t g = 0; g < ng; g++) state[g] = fig_indel_gap_on(unmapped_model != 0, filled_len[g], draw_len[2 * g], draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+    return 0;
+}
+
+// 1 iff a scored read of `len` bases drawn at o is aligned to a string of n bases; the t-th diagonal of the end's tie order
+extern "C" int fighost_indel_aligned(int32_t o, int32_t len, int32_t n) { return fig_indel_aligned(o, len, n) ? 1 : 0; }
+extern "C" int fighost_indel_end_order(int t) { return fig_indel_end_order(t); }
+
+// call [n] of `n` columns from their three counts; fighost_indel_call_end: the junction's, from ins_end and the last column's cover
+extern "C" int fighost_indel_call(int64_t n, const int32_t *del_reads, const int32_t *ins_reads, const int32_t *cover, char *call) {
+    for (int64_t i = 0; i < n; i++) call[i] = fig_indel_call(del_reads[i], ins_reads[i], cover[i]);
+    return 0;
+}
+extern "C" int fighost_indel_call_end(int32_t ins_end, int32_t cover_last) { return fig_indel_majority(ins_end, cover_last) ? 'I' : '.'; }
+
+// gapindel.txt of the WHOLE gap set (FIGFILL_INDEL=1): call [str_off[n_gaps]] indexed like the strings, call_end and state [n_gaps]
+extern "C" int fighost_run_write_indel(void *h, const int32_t *filled_len, const int64_t *str_off, const char *call, const char *call_end, const uint8_t *state,
+                                       char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size();
+    fighost::Results R = side_results(r, filled_len, str_off);
+    R.indel_call.assign(call, call + (size_t)str_off[ng]);
+    R.indel_call_end.assign(call_end, call_end + ng);
+    R.indel_state.assign(state, state + ng);
+    std::string e;
+    return written(fighost::write_indel(r->a, r->B, R, e), e, err, errcap);
 }

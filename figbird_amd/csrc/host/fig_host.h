@@ -94,6 +94,9 @@ struct Results {
     std::vector<uint8_t> place_pq, place_state;
     // per-base quality summed over read placements (fig_gap_softqual), when asked for: Phred [str.size()] indexed like str, and FIG_SOFTQ_* [n_gaps]
     std::vector<uint8_t> softq_phred, softq_state;
+    // indel evidence (fig_gap_indel), when asked for: call [str.size()] indexed like str, call_end and FIG_INDEL_* [n_gaps]
+    std::string indel_call, indel_call_end;
+    std::vector<uint8_t> indel_state;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
@@ -111,6 +114,9 @@ bool write_softquality(const RunArgs &a, const Batch &b, const Results &r, std::
 // as in gapout.txt, state = FIG_PLACE_*, R = the gap's unmapped read count, Q = R characters: Phred+33 of the read's pq, or '~'
 // for a read that was not scored
 bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gapindel.txt (no counterpart in the reference): per gap `g contig start G0 n state C E`, tab-separated, the first five fields as in
+// gapout.txt, state = FIG_INDEL_*, C = the n characters of fig_gap_indel::call ('D', 'I' or '.'; empty for n <= 0), E = call_end
+bool write_indel(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // filledContigs.fa + Ncount.txt (FillGaps.cpp:708-926)
 bool write_scaffold(const RunArgs &a, const Scaffold &sc, const Batch &b, const Results &r, std::string &err);
 

@@ -44,6 +44,9 @@ PLANES = (
     ("placement", "pst", lambda r: r.placement.state, "gap", (), np.uint8, 0),
     ("softquality", "sph", lambda r: r.softqual.phred, "byte", (), np.uint8, 0),
     ("softquality", "sst", lambda r: r.softqual.state, "gap", (), np.uint8, 0),
+    ("indel", "icl", lambda r: r.indel.call, "byte", (), np.uint8, ord(".")),
+    ("indel", "ice", lambda r: r.indel.call_end, "gap", (), np.uint8, ord(".")),
+    ("indel", "ist", lambda r: r.indel.state, "gap", (), np.uint8, 0),
 )
 
 
@@ -59,9 +62,10 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     # the per-base Phred (fig_gap_quality); FIGFILL_PLACEMENT=1: also gapplacement.txt, the placement confidence per drawn unmapped
     # read (fig_read_placement) -- any of them runs the fill with the support call; FIGFILL_QUALITY_MINPQ=<k> (only with
     # FIGFILL_QUALITY=1): the quality leaves out the scored reads with pq < k; FIGFILL_SOFTQUALITY=1: also gapsoftquality.txt, the
-    # per-base Phred summed over read placements (fig_gap_softqual)
-    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality")}
-    support, quality, placement, softquality = on["support"], on["quality"], on["placement"], on["softquality"]
+    # per-base Phred summed over read placements (fig_gap_softqual); FIGFILL_INDEL=1: also gapindel.txt, the indel call per filled base
+    # (fig_gap_indel)
+    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality", "indel")}
+    support, quality, placement, softquality, indel = on["support"], on["quality"], on["placement"], on["softquality"], on["indel"]
     min_pq = _env_int("FIGFILL_QUALITY_MINPQ") if quality else None
     if min_pq is not None and min_pq < 0:
         min_pq = None
@@ -128,8 +132,8 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
             preset = np.zeros(max(n, 1), dtype=np.uint8)
             host.fighost_run_ot_presets(h, api._p(reach, api.c_u8_p), api._p(preset, api.c_u8_p))
             eng.set_ot_preset(preset[mine] if len(mine) else np.zeros(0, dtype=np.uint8))
-            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality, quality=quality, placement=placement, min_pq=min_pq,
-                                  softqual=softquality)
+            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality or indel, quality=quality, placement=placement, min_pq=min_pq,
+                                  softqual=softquality, indel=indel)
             st = eng.stats()
             eng.close()
         except Exception as e:
@@ -194,6 +198,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 if wrc == 0 and softquality:
                     wrc = host.fighost_run_write_softquality(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
                                                              api._p(G["sph"], api.c_u8_p), api._p(G["sst"], api.c_u8_p), err, 512)
+                if wrc == 0 and indel:
+                    wrc = host.fighost_run_write_indel(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
+                                                       C.cast(G["icl"].ctypes.data, C.c_char_p), C.cast(G["ice"].ctypes.data, C.c_char_p), api._p(G["ist"], api.c_u8_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

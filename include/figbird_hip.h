@@ -276,6 +276,79 @@ typedef struct fig_gap_softqual {
     uint8_t *state;    /* [n_gaps] FIG_SOFTQ_* */
 } fig_gap_softqual;
 
+/* Optional indel evidence per filled base (fig_batch_indel): a gapped realignment of every drawn read.  The planes above score reads
+ * against the emitted sequence with substitutions only: a homopolymer that came out one base short shows as a run of mismatches in
+ * every read that spans it, and nothing names the missing base.  Here each drawn read is realigned around its drawn offset by a
+ * banded dynamic program with the model's own insertion and deletion rates, and per column the reads that ask for an edit are counted.
+ * Terms not redefined here mean what they mean for fig_read_placement: the sequence S(x) of a gap, n, the tables lm, le, lt and lq,
+ * the index k and the skipping of a read base outside ACGT, which gaps are on and which reads are scored.
+ *
+ * Gaps and reads.  A gap is FIG_INDEL_ON iff it is FIG_PLACE_ON.  A scored read is ALIGNED iff its drawn offset o* satisfies
+ * -(len-1) <= o* <= n-1; the insert size takes no part.  Every other read is unaligned.
+ *
+ * Tables, built on the host with the C library's log10 (-inf is kept): lI[k] = log10(in_pos_dist[k]) + lq, one IEEE addition (an
+ * inserted read base is uniform over the four bases); lD[k] = log10(del_pos_dist[k]).
+ *
+ * Band.  W = 7 (FIG_INDEL_W), diagonals d in [-7, 7].  Cell (i, d): i read bases are consumed and the next column is x = o* + i + d.
+ *   H(0, d) = 0.0 for every d: the start is free.
+ *   For i = 1 .. len, with j = i-1 and (s, k) of read base j:
+ *     diag = H(i-1, d) if base j is outside ACGT (skipped, nothing added), else H(i-1, d) + t, where with c = S(o* + j + d):
+ *            t = lq if c is N, lm[k] if c == s, else le[k] + lt[c][s];
+ *     ins  = H(i-1, d+1) + lI[k], or -inf for d = 7;
+ *     H(i, d) = diag with back-pointer DIAG if diag >= ins, else ins with back-pointer INS.
+ *   Then, for 1 <= i <= len-1 only, in ascending d from -6: v = H(i, d-1) + lD[k], k that of base i-1; if v > H(i, d) (strictly),
+ *   H(i, d) = v with back-pointer DEL.
+ * Every + is one IEEE double addition; only -inf can meet -inf, so no NaN arises.
+ *
+ * End.  ll_gapped is the greatest H(len, d); ties go to the first d in the order 0, -1, +1, -2, +2, ..., -7, +7: that d is d_end.
+ * ll_flat is the sum along d = 0 alone: the same terms from 0.0, with no INS or DEL; ll_gapped >= ll_flat, exactly.  If ll_gapped
+ * is -inf the read reports ll_flat, ll_gapped and zeros: it has no events and no cover.
+ *
+ * Path and events.  The path is the traceback from (len, d_end) along the back-pointers to row 0, where d is d_start.  An event is a
+ * maximal run of INS steps or of DEL steps; n_ins is the number of inserted read bases, n_del the number of deleted columns.  Each
+ * event is LEFT-NORMALISED before it is reported, so that the reads of one homopolymer agree on a column:
+ *   a DEL run over columns [x, x+m): while the path step before the run is DIAG (some read base on column x-1) and
+ *   S(x-1) == S(x+m-1) as codes, x -= 1;
+ *   an INS run of read bases [i, i+m) whose next column is x: while the step before the run is DIAG (base i-1 on column x-1) and bases
+ *   i-1 and i+m-1 have equal codes and equal N bits, i -= 1 and x -= 1.
+ * This never looks past the path's start or another event, and the back-pointers are not changed by it.
+ *
+ * Planes, over the columns 0 <= x < n of a gap that is on, compacted like str:
+ *   del_reads[x]  aligned reads with a normalised DEL run covering x
+ *   ins_reads[x]  aligned reads with a normalised INS run whose next column is x
+ *   ins_end[g]    the same for next column n, the right junction
+ *   cover[x]      aligned reads with finite ll_gapped whose path spans x: o* + d_start <= x <= o* + len - 1 + d_end
+ * They are integers: the order of accumulation does not matter.
+ *
+ * Call (host).  call[x] is 'D' if del_reads[x] >= 2 and 2 * del_reads[x] > cover[x]; else 'I' under the same rule on ins_reads[x];
+ * else '.'.  call_end[g] likewise, from ins_end[g] and cover[n-1].
+ *
+ * Defaults, written by the library whatever the buffers held.  Off gaps: all planes 0, calls '.'.  Unaligned reads:
+ * ll_flat = ll_gapped = 0.0, n_ins = n_del = d_end = 0, d_start = INT32_MIN.
+ *
+ * Limits of the number: the band -- a net shift of 8 or more is not found; no insert-size term -- a read wholly on d != 0 is
+ * fig_read_placement's business; a linear gap cost from the position rates only (the length distributions are not in fig_model);
+ * 1 - e[k] instead of 1 - e - ins - del under a match, so that a path without indels scores fig_read_placement's terms; reads are
+ * taken as independent; partial reads and undrawn reads take no part. */
+#define FIG_INDEL_OFF 0
+#define FIG_INDEL_ON  1
+#define FIG_INDEL_W   7
+typedef struct fig_gap_indel {
+    double  *ll_flat;    /* [n_ureads] */
+    double  *ll_gapped;  /* [n_ureads] */
+    int32_t *n_ins;      /* [n_ureads] */
+    int32_t *n_del;      /* [n_ureads] */
+    int32_t *d_end;      /* [n_ureads] */
+    int32_t *d_start;    /* [n_ureads] */
+    int32_t *del_reads;  /* [str_off[n_gaps]] */
+    int32_t *ins_reads;  /* [str_off[n_gaps]] */
+    int32_t *cover;      /* [str_off[n_gaps]] */
+    int32_t *ins_end;    /* [n_gaps] */
+    char    *call;       /* [str_off[n_gaps]] 'D', 'I' or '.' */
+    char    *call_end;   /* [n_gaps] 'I' or '.' */
+    uint8_t *state;      /* [n_gaps] FIG_INDEL_* */
+} fig_gap_indel;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -344,6 +417,12 @@ int fig_batch_placement(fig_ctx *ctx, const fig_gap_results *filled, const int32
  * on, columns, reads, active placements, HIP-event milliseconds of each of the two launches. */
 int fig_batch_softqual(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin,
                        fig_read_placement *placement_or_null, fig_gap_softqual *out);
+
+/* Indel evidence of the drawn unmapped reads of `filled` against the RESIDENT batch (see fig_gap_indel); `filled` and origin as for
+ * fig_batch_placement (draw_isz is not read), and the same FIG_EINVAL conditions, a NULL member of `out` included.  Reads the resident
+ * batch and the model and writes neither.  With FIG_SCHED_LOG set, one "[figindel]" line on stderr: gaps on, reads aligned, reads
+ * with an event, columns called, HIP-event milliseconds of the kernel. */
+int fig_batch_indel(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, fig_gap_indel *out);
 
 int fig_get_stats(const fig_ctx *ctx, fig_stats *out);
 
