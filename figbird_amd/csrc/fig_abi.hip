@@ -149,21 +149,47 @@ FIG_D void fig_cont_publish(FigEng &E, const FigDevBatch &B, const FigKernArgs &
     __syncthreads();
     if (E.tid == 0) {
         bool ok = true;
+        int n = c.n, rank = c.rank;
         if (c.kind == FIG_CONT_EVAL) {
             const long long live = (long long)gridDim.x - fig_ld_relaxed(&B.cont_hdr->exited);
-            ok = live * 100 >= (long long)c.n * A.cont_live;
+            ok = live * 100 >= (long long)n * A.cont_live;
+            // a widened chunk the emptying launch can no longer take: as many candidates as there are workgroups left, if that is
+            // still the chunk the gap would have had without the widening (c.pad); else the host's, like any other
+            if (!ok && n > c.pad && A.cont_live > 0) {
+                const long long fit = live * 100 / A.cont_live;
+                // (rank: the narrower chunk leaves candidates for at least one more chunk than fig_wide_rank counted for the wide
+                // one; the exact count needs the gap's slots and range, which the publisher no longer has -- the rank only orders claims)
+                if (fit >= c.pad && fit >= 1) { n = (int)(fit < n ? fit : n); rank = rank + 1; ok = true; atomicAdd(&B.counters[FIG_CNT_NARROW], 1ull); }
+            }
         }
         if (ok) {
             const int idx = atomicAdd(&B.cont_hdr->tail, 1);
             if (idx < B.cont_cap) {
                 FigCont *e = B.cont + idx;
-                e->gap = c.gap; e->j0 = c.j0; e->n = c.n; e->kind = c.kind; e->next = 0; e->rank = c.rank; e->pad = 0;
+                e->gap = c.gap; e->j0 = c.j0; e->n = n; e->kind = c.kind; e->next = 0; e->rank = rank; e->pad = 0;
+                atomicAdd(&B.cont_hdr->open, n);
                 __hip_atomic_store(&e->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
                 if (c.kind == FIG_CONT_EVAL) atomicAdd(&B.counters[FIG_CNT_CONT], 1ull);
             }
         }
     }
     __syncthreads();
+}
+
+// Idle-driven widening (FIG_WIDE_IDLE): workgroups of the launch that would find nothing to claim once everything unclaimed is
+// handed out -- live workgroups less the host-planned items not yet popped and the published items not yet claimed.  A
+// snapshot of three counters, the same in every lane; nothing depends on its being exact.
+FIG_D int fig_cont_spare(FigEng &E, const FigDevBatch &B, const FigKernArgs &A, int n_items) {
+    if (E.tid == 0) {
+        const long long live = (long long)gridDim.x - fig_ld_relaxed(&B.cont_hdr->exited);
+        const long long popped = fig_ld_relaxed(B.queue_head + A.qsel), open = fig_ld_relaxed(&B.cont_hdr->open);
+        const long long waiting = (popped < n_items ? n_items - popped : 0) + (open > 0 ? open : 0);
+        E.S->bc_i = live > waiting ? (int)(live - waiting) : 0;
+    }
+    __syncthreads();
+    const int spare = E.S->bc_i;
+    __syncthreads();
+    return spare;
 }
 
 // Claim one item of the continuations published so far: the entry whose gap has the longest chain of chunks ahead (FIG_CONT_PRIO=0:
@@ -197,7 +223,7 @@ FIG_D bool fig_cont_pop(FigEng &E, const FigDevBatch &B, const FigKernArgs &A, F
         __syncthreads();
         k = S.bc_j;
         __syncthreads();
-        if (k < B.cont[idx].n) { __threadfence(); out = B.cont[idx]; return true; }
+        if (k < B.cont[idx].n) { if (E.tid == 0) atomicSub(&B.cont_hdr->open, 1); __threadfence(); out = B.cont[idx]; return true; }
     }
     return false;
 }
@@ -214,7 +240,8 @@ __global__ void __launch_bounds__(NT, (NT <= 256 ? 2 : 1)) fig_eval_kernel(FigDe
         fig_item_eval<LDS_TAB>(E, work, it);
         if (A.cont && it.chunk > 0 && fig_chunk_finished(E, B, it.gap, it.chunk)) {
             FigCont nx;
-            fig_item_continue(E, work, it.gap, it.chunk, A.minc, nx);
+            const int spare = (A.wide & FIG_WIDE_IDLE) ? fig_cont_spare(E, B, A, n_items) : 0;
+            fig_item_continue(E, work, it.gap, it.chunk, A.minc, FigWide{A.wide, A.wide_base, A.wide_cap}, spare, nx);
             fig_cont_publish(E, B, A, nx);
         }
     };
@@ -306,7 +333,7 @@ struct FigTmpBufs {
 // classes' workgroups.
 struct FigLane { hipStream_t stream = nullptr; hipEvent_t done = nullptr; int32_t *queue_head = nullptr; uint8_t *scratch = nullptr; FigItem *d_items = nullptr; FigEntry *d_entries = nullptr; size_t cap = 0;   // cap: items / entries the buffers hold
                  FigGapCtl *h_ctl = nullptr; FigItem *h_items = nullptr; FigEntry *h_entries = nullptr; int qsel = 0;   // h_*: pinned, so the copies run on the DMA engines and never wait for a CU
-                 uint8_t *d_cont = nullptr; int cont_cap = 0; };   // continuation array of the lane's eval launches: FigContHdr, then cont_cap entries
+                 uint8_t *d_cont = nullptr; int cont_cap = 0; int wide = 0; };   // continuation array of the lane's eval launches: FigContHdr, then cont_cap entries
 
 struct fig_ctx {
     int device = 0;
@@ -328,7 +355,7 @@ struct fig_ctx {
     std::vector<DevBuf> bufs;
     int64_t n_gaps = 0, n_ureads = 0, n_preads = 0, str_total = 0;
     std::vector<int64_t> h_str_off;
-    int nslots = 32;
+    int nslots = 32, nslots_wide = 32;    // base slots of a gap's chunk; the wide cap the resident batch was packed with (FIG_SLOTS_WIDE, possibly halved at upload)
     std::vector<FigLane> lanes;
     fig_stats stats;
     int sh_on = FIG_SH_SC;            // FIG_ESTEP / FIG_SH_CHUNKS, read once at fig_ctx_create
@@ -456,9 +483,10 @@ static hipError_t launch_one(void (*k)(P...), size_t lds, int nt, int blocks, hi
 }
 
 template <bool LDS_TAB, int NT>
-static hipError_t launch_kind(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, FigKind kind, int blocks, const void *list, int n, int qsel) {
+static hipError_t launch_kind(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, FigKind kind, int blocks, const void *list, int n, int qsel, int wide) {
     FigKernArgs A = fig_kargs_of(c.c, qsel, ctx->sh_on);
-    if (kind == FIG_K_EVAL) { const FigKnobs &kn = ctx->fill_knobs; A.cont = kn.cont && db.cont_cap > 0; A.minc = kn.minc; A.cont_live = kn.cont_live; A.cont_prio = kn.cont_prio; }
+    if (kind == FIG_K_EVAL) { const FigKnobs &kn = ctx->fill_knobs; A.cont = kn.cont && db.cont_cap > 0; A.minc = kn.minc; A.cont_live = kn.cont_live; A.cont_prio = kn.cont_prio;
+                              A.wide = A.cont ? wide : 0; A.wide_base = ctx->nslots; A.wide_cap = ctx->nslots_wide; }
     switch (kind) {
         case FIG_K_FILL: return launch_one(fig_fill_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
         case FIG_K_BEGIN: return launch_one(fig_begin_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
@@ -469,28 +497,48 @@ static hipError_t launch_kind(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevB
     return hipErrorInvalidValue;
 }
 
-static hipError_t launch_any(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, FigKind kind, int blocks, const void *list, int n, int qsel = 0) {
-    if (c.c.tiles > 0) return launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);      // LDS-tiled: the LDS code path with a streamed table
-    if (c.c.lds_tab) return c.c.nt == 256 ? launch_kind<true, 256>(ctx, c, db, stream, kind, blocks, list, n, qsel) : launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);
-    return launch_kind<false, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel);
+static hipError_t launch_any(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevBatch &db, hipStream_t stream, FigKind kind, int blocks, const void *list, int n, int qsel = 0, int wide = 0) {
+    if (c.c.tiles > 0) return launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel, wide);      // LDS-tiled: the LDS code path with a streamed table
+    if (c.c.lds_tab) return c.c.nt == 256 ? launch_kind<true, 256>(ctx, c, db, stream, kind, blocks, list, n, qsel, wide) : launch_kind<true, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel, wide);
+    return launch_kind<false, 512>(ctx, c, db, stream, kind, blocks, list, n, qsel, wide);
 }
 
-extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
-    if (!ctx || !b) return FIG_EINVAL;
-    if (!ctx->have_model) return FIG_EINVAL;
-    hipSetDevice(ctx->device);
+// One attempt of fig_batch_upload with the wide cap `wide_cap` (>= the base slots; `wide_asked`: what the knobs asked for, for the log)
+static int fig_upload_once(fig_ctx *ctx, const fig_gap_batch *b, int wide_cap, int wide_asked) {
     free_batch(ctx);
     const fig_model *m = &ctx->hm;
     hipEventRecord(ctx->ev0, ctx->stream);
     FigPacked K;
+    const FigKnobs up_knobs = fig_knobs_from_env(0);
+    K.nslots_wide = std::max(K.nslots, wide_cap);
     int prc = fig_pack(m, b, sizeof(FigState), K);
     if (prc) return prc;
+    // The persistent slab with wide slots: within a quarter of the device memory that is free now, and allocated before anything
+    // else, so that an upload that succeeds with the base slots still does -- the wide cap is halved down to the base until it fits.
+    void *persist_mem = nullptr;
+    const int wide_first = K.nslots_wide;
+    K.nslots_wide = K.nslots; fig_pack_persist(K, sizeof(FigState));
+    const int64_t persist_base = K.persist_total;      // (what the slab takes with the base slots, for the log)
+    K.nslots_wide = wide_first; fig_pack_persist(K, sizeof(FigState));
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) mem_free = 0;
+    while (true) {
+        const bool fits = (size_t)K.persist_total + 256 <= mem_free / 4 || K.nslots_wide <= K.nslots;
+        if (fits && hipMalloc(&persist_mem, (size_t)K.persist_total + 256) == hipSuccess) break;
+        persist_mem = nullptr; (void)hipGetLastError();
+        if (K.nslots_wide <= K.nslots) return FIG_ENOMEM;
+        K.nslots_wide = std::max(K.nslots, K.nslots_wide / 2);
+        fig_pack_persist(K, sizeof(FigState));
+    }
+    { DevBuf pb; pb.p = persist_mem; ctx->bufs.push_back(pb); }
     int64_t ng = K.n_gaps;
     ctx->h_order = K.order; ctx->h_str_off = K.str_off;
     ctx->str_total = K.str_total; ctx->n_gaps = ng;
     ctx->n_ureads = (int64_t)K.u_pos.size(); ctx->n_preads = (int64_t)K.p_pos.size();
     ctx->classes.clear();
-    const bool log = fig_knobs_from_env(0).log;
+    const bool log = up_knobs.log;
+    if (log) fprintf(stderr, "[figsched] persistent slab: %lld B with %d base slots per gap, %lld B with min(candidates, %d) slots per gap%s\n", (long long)persist_base, K.nslots,
+                     (long long)K.persist_total, K.nslots_wide, K.nslots_wide < wide_asked ? " (FIG_SLOTS_WIDE halved: what was asked for does not fit, the slab in a quarter of the free device memory or a later allocation)" : "");
     for (const FigLaunchClass &lc : K.classes) {
         fig_ctx::Cls c;
         c.c = lc;
@@ -535,13 +583,13 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     size_t total_blocks = 0;
     for (const fig_ctx::Cls &c : ctx->classes) total_blocks += (size_t)c.capacity;
     if ((rc = dev_alloc(ctx, (size_t)stride * std::max<size_t>(total_blocks, 1), &p))) return rc; db.scratch = (uint8_t *)p;
-    if ((rc = dev_alloc(ctx, (size_t)K.persist_total + 256, &p))) return rc; db.persist = (uint8_t *)p;
+    db.persist = (uint8_t *)persist_mem;
     if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl), &p))) return rc; db.gapctl = (FigGapCtl *)p;
     if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1) * 4, &p))) return rc; db.gap_pending = (int32_t *)p;
     if ((rc = dev_alloc(ctx, (size_t)std::max<int64_t>(ng, 1), &p))) return rc; ctx->d_ot = (uint8_t *)p; db.ot_preset = ctx->d_ot;
     ctx->h_ot = K.ot_preset;
     FIG_HIP(hipMemcpyAsync(ctx->d_ot, ctx->h_ot.data(), (size_t)std::max<int64_t>(ng, 1), hipMemcpyHostToDevice, ctx->stream));
-    ctx->nslots = K.nslots;
+    ctx->nslots = K.nslots; ctx->nslots_wide = K.nslots_wide;
     {   size_t blk = 0;
         for (size_t ci = 0; ci < ctx->classes.size(); ci++) {
             const fig_ctx::Cls &c = ctx->classes[ci];
@@ -550,10 +598,11 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
             if (hipStreamCreate(&l.stream) != hipSuccess || hipEventCreateWithFlags(&l.done, hipEventDisableTiming) != hipSuccess) return FIG_EHIP;
             l.queue_head = db.queue_head + 16 * (ci + 1);
             l.scratch = db.scratch + (size_t)stride * blk; blk += (size_t)c.capacity;
-            l.cap = (size_t)std::max(c.c.q_end - c.c.q_begin, 1) * (size_t)(K.nslots + 1);
+            const std::vector<int> lane_ids(K.order.begin() + c.c.q_begin, K.order.begin() + c.c.q_end);
+            l.cap = fig_lane_items(lane_ids, K.gaps);
             if ((rc = dev_alloc(ctx, l.cap * sizeof(FigItem), &p))) return rc; l.d_items = (FigItem *)p;
             if ((rc = dev_alloc(ctx, l.cap * sizeof(FigEntry), &p))) return rc; l.d_entries = (FigEntry *)p;
-            l.cont_cap = fig_cont_capacity(std::vector<int>(K.order.begin() + c.c.q_begin, K.order.begin() + c.c.q_end), K.gaps, fig_knobs_from_env(0).minc);
+            l.cont_cap = fig_cont_capacity(lane_ids, K.gaps, up_knobs.minc);
             if ((rc = dev_alloc(ctx, sizeof(FigContHdr) + (size_t)l.cont_cap * sizeof(FigCont), &p))) return rc; l.d_cont = (uint8_t *)p;
             if (hipHostMalloc((void **)&l.h_ctl, (size_t)std::max<int64_t>(ng, 1) * sizeof(FigGapCtl), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
             if (hipHostMalloc((void **)&l.h_items, l.cap * sizeof(FigItem), hipHostMallocDefault) != hipSuccess) return FIG_ENOMEM;
@@ -573,6 +622,24 @@ extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     ctx->have_batch = true;
     if (!K.ot_given && m->partial_flag && ng > 0 && (rc = fig_ot_carry_measured(ctx, ng))) { free_batch(ctx); return rc; }
     return FIG_OK;
+}
+
+// Wide slots (FIG_SLOTS_WIDE) only where the fill would widen: the mode's FIG_WIDE as the knobs stand at upload (a partial-mode
+// batch keeps the 64 base slots unless FIG_SCHED=continuous and FIG_WIDE ask otherwise; a fill that asks for widening on such
+// a batch gets none).  An upload must not fail where it succeeds with the base slots: when any allocation of an attempt fails,
+// the attempt is repeated with half the wide cap, down to the base.
+extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
+    if (!ctx || !b) return FIG_EINVAL;
+    if (!ctx->have_model) return FIG_EINVAL;
+    hipSetDevice(ctx->device);
+    const FigKnobs kn = fig_knobs_from_env(ctx->hm.unmapped_flag);
+    const int base = FigPacked().nslots;
+    const int asked = kn.wide ? std::max(base, std::min(kn.slots_wide, FIG_SLOTS_WIDE_MAX)) : base;
+    for (int w = asked;; w = std::max(base, w / 2)) {
+        const int rc = fig_upload_once(ctx, b, w, asked);
+        if (rc != FIG_ENOMEM || w <= base) return rc;
+        (void)hipGetLastError();
+    }
 }
 
 // Per gap of the resident batch: 1 iff the gap's candidate loop gets to Figbird.cpp:6317 (fig_engine_sched.h: fig_gap_probe).
@@ -626,7 +693,7 @@ static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln, 
     const int capacity = std::max(1, c.capacity);      // workgroups the device holds for this class (not capped by the gap count)
     // every persistent launch pops from one of the lane's two queue heads and zeroes the other for its successor
     auto launch = [&](FigKind kind, int n_work, const void *list) {
-        hipError_t er = launch_any(ctx, c, db, stream, kind, std::min(capacity, n_work), list, n_work, ln.qsel);
+        hipError_t er = launch_any(ctx, c, db, stream, kind, std::min(capacity, n_work), list, n_work, ln.qsel, ln.wide);
         ln.qsel ^= 1; nl++;
         return er;
     };
@@ -641,7 +708,8 @@ static int run_class_parallel(fig_ctx *ctx, const fig_ctx::Cls &c, FigLane &ln, 
     while (true) {
         if ((e = hipMemcpyAsync(ctl, db.gapctl, ctl_bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess) return fail(e);
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return fail(e);
-        fig_plan_round(ids, ctl, capacity, c.c.nsplit, ctx->nslots, knobs.minc, knobs.ipw, n_active_max, R);
+        fig_plan_round(ids, ctl, capacity, c.c.nsplit, ctx->nslots, knobs.wide, ctx->nslots_wide, knobs.wide_max_active, knobs.minc, knobs.ipw, n_active_max, R);
+        ln.wide = fig_wide_for_lane(knobs.wide, n_active_max, knobs.wide_max_active);      // (the eval launch of this round widens as the planner did)
         if (knobs.log) { double t = now(); fprintf(stderr, "[figsched] capG=%d round %d: active=%d chunk=%d items=%d blocks=%d  %.1f ms\n", c.c.capG, round, last_active, last_chunk, last_items, capacity, t - t_prev); t_prev = t; }
         round++;
         if (R.n_active == 0) break;
@@ -758,6 +826,7 @@ extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fi
       fprintf(stderr, "[figprof] barrier wait %.3f of %.3f wave-Gcycles = %.1f %%\n", cnt[FIG_CNT_WAIT] / 1e9, wave / 1e9, wave ? 100.0 * cnt[FIG_CNT_WAIT] / wave : 0.0); }
 #endif
     if (knobs.log) fprintf(stderr, "[figsched] useful flops %.4g, speculative evaluations executed %.4g (%.1f %% discarded)\n", (double)cnt[FIG_CNT_FLOPS], (double)cnt[FIG_CNT_SPEC], cnt[FIG_CNT_SPEC] ? 100.0 * (1.0 - ((double)cnt[FIG_CNT_FLOPS] / (double)cnt[FIG_CNT_SPEC])) : 0.0);
+    if (knobs.log && knobs.wide) fprintf(stderr, "[figsched] widened chunks narrowed to the live workgroups: %llu\n", cnt[FIG_CNT_NARROW]);
     fig_stats_from_counters(cnt, ctx->stats);
     int rc = fig_compact_results(ng, hstr.data(), ctx->h_str_off.data(), out);
     if (!rc && sup) fig_compact_support(ng, hsup.data(), ctx->h_str_off.data(), out, sup->counts);

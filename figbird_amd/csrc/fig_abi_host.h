@@ -209,6 +209,16 @@ struct FigKnobs {
     // (0: always -- one workgroup may then run a whole chain of chunks alone); FIG_CONT_PRIO=0 hands continuations out oldest
     // first instead of longest remaining chain first
     bool cont; int cont_cap, cont_live, cont_prio;
+    // FIG_WIDE=0|grow|idle|both: wide chunks for the gaps that keep running, in the continuous form only (fig_engine_sched.h:
+    // fig_wide_chunk).  grow: a continued chunk may be twice the gap's last one; idle: it may take the workgroups that would
+    // find nothing to do; 0: the schedule without it, launch for launch.  Default: grow in unmapped mode (DESIGN 5b has the
+    // measurements), 0 in partial mode, whose gaps stop after a fifth of their candidates.  FIG_SLOTS_WIDE=<n>, read at
+    // fig_batch_upload: the wide cap W -- a gap owns min(its candidates, W) slots; default 256, never below the 64 base slots
+    // FIG_WIDE_MAX_ACTIVE=<n>, default 96: growth only while the lane's largest active set so far is at most n gaps.  A lane
+    // with hundreds of active gaps is throughput-bound, not chain-bound: grown chunks there only add discarded evaluations and
+    // more gaps' reads in flight (2 048 gaps: +6 % with growth everywhere); 96 is where fig_plan_round starts
+    // lengthening its rounds for the same reason.  Idle-driven widening needs no gate: such a lane has no spare workgroups
+    int wide, slots_wide, wide_max_active;
     bool lanes_serial;   // FIG_LANES=serial: the class lanes one after the other on the calling thread
     bool log;            // FIG_SCHED_LOG
     int minc;            // FIG_MIN_CHUNK: candidates per gap and round, at least
@@ -218,6 +228,8 @@ struct FigKnobs {
     int sh_on;
 };
 
+#define FIG_WIDE_DEFAULT_UNMAPPED FIG_WIDE_GROW
+#define FIG_SLOTS_WIDE_MAX 4096      // FIG_SLOTS_WIDE at most
 static FigKnobs fig_knobs_from_env(int unmapped) {
     FigKnobs k;
     const char *sched = getenv("FIG_SCHED"), *ser = getenv("FIG_LANES"), *mc = getenv("FIG_MIN_CHUNK"), *ipw = getenv("FIG_ITEMS_PER_WG");
@@ -228,6 +240,12 @@ static FigKnobs fig_knobs_from_env(int unmapped) {
     k.cont_cap = cc ? std::max(1, atoi(cc)) : FIG_CONT_CAP_MAX;
     k.cont_live = cl ? std::max(0, atoi(cl)) : 100;
     k.cont_prio = cp ? (atoi(cp) != 0) : 1;
+    const char *wd = getenv("FIG_WIDE"), *sw = getenv("FIG_SLOTS_WIDE");
+    k.wide = !wd ? (unmapped ? FIG_WIDE_DEFAULT_UNMAPPED : 0) : !strcmp(wd, "grow") ? FIG_WIDE_GROW : !strcmp(wd, "idle") ? FIG_WIDE_IDLE : !strcmp(wd, "both") ? (FIG_WIDE_GROW | FIG_WIDE_IDLE) : 0;
+    if (!k.cont) k.wide = 0;
+    k.slots_wide = sw ? atoi(sw) : 256;
+    const char *wa = getenv("FIG_WIDE_MAX_ACTIVE");
+    k.wide_max_active = wa ? std::max(0, atoi(wa)) : 96;
     k.lanes_serial = ser && strcmp(ser, "serial") == 0;
     k.log = getenv("FIG_SCHED_LOG") != nullptr;
     k.minc = mc ? std::max(1, atoi(mc)) : 16;
@@ -242,9 +260,17 @@ static FigKnobs fig_knobs_from_env(int unmapped) {
 struct FigRound { std::vector<FigItem> items; std::vector<FigEntry> entries; int chunk = 0, n_active = 0; };
 
 // ids: the lane's gaps in cost order; ctl: gapctl snapshot of the batch; capacity: workgroups the device holds for this class;
-// nsplit: lanes the class runs as; slots_cap: candidate slots per gap; n_active_max: the lane's largest active set so far
-// (in/out).  n_active == 0 on return: nothing left, no round.
-static void fig_plan_round(const std::vector<int> &ids, const FigGapCtl *ctl, int capacity, int nsplit, int slots_cap, int minc, double ipw_base,
+// nsplit: lanes the class runs as; slots_cap: candidate slots of a gap's chunk; n_active_max: the lane's largest active set so far
+// (in/out).  n_active == 0 on return: nothing left, no round.  wide_mode / wide_cap (FIG_WIDE, FIG_SLOTS_WIDE): a gap that
+// comes back with j > 0 has had its last chunk (FigGapCtl::last) consumed to its end and may get a wider one by the rule of
+// fig_wide_chunk -- grown in any round, and up to the lane's share of workgroups the round leaves idle when the round admits
+// every active gap and still holds fewer items than that share.  A gap's first chunk (j == 0) and everything with
+// wide_cap <= slots_cap or wide_mode 0 is as without it; growth is off once the lane's active set has been above wide_max_active.
+static inline int fig_wide_for_lane(int wide_mode, int n_active_max, int wide_max_active) {      // FIG_WIDE bits in force for a lane (FIG_WIDE_MAX_ACTIVE)
+    return n_active_max > wide_max_active ? (wide_mode & ~FIG_WIDE_GROW) : wide_mode;
+}
+
+static void fig_plan_round(const std::vector<int> &ids, const FigGapCtl *ctl, int capacity, int nsplit, int slots_cap, int wide_mode, int wide_cap, int wide_max_active, int minc, double ipw_base,
                            int &n_active_max, FigRound &R) {
     R.items.clear(); R.entries.clear();
     R.chunk = 0; R.n_active = 0;
@@ -261,6 +287,7 @@ static void fig_plan_round(const std::vector<int> &ids, const FigGapCtl *ctl, in
     // round (121 rounds per lane of 1920 items over 385 active gaps: every round ends with a tail of the long items of
     // the most expensive gaps), 99.8 s with 48 and 98.5 s with 96 -- while 48 costs the 512-gap batch 3 %.
     n_active_max = std::max(n_active_max, R.n_active);
+    wide_mode = fig_wide_for_lane(wide_mode, n_active_max, wide_max_active);
     const double ipw = ipw_base * std::min(8.0, std::max(1.0, n_active_max / 96.0));      // by the lane's largest active set: the rounds stay long to the end of a big fill
     const double share = rem_total > 0 ? (ipw * capacity / (double)std::max(1, nsplit)) / (double)rem_total : 1.0;
     // Admission: a gap gets at least `minc` candidates in a round it takes part in, and gaps are admitted in cost order
@@ -277,10 +304,22 @@ static void fig_plan_round(const std::vector<int> &ids, const FigGapCtl *ctl, in
         int want = (int)std::ceil((range - j) * share);
         want = std::min(std::max(want, minc), slots_cap);
         int n = std::max(0, std::min(want, range - j));       // (0: replayed with nothing to evaluate: the replay closes the gap)
-        R.chunk = std::max(R.chunk, n);
+        if (j > 0 && n > 0 && (wide_mode & FIG_WIDE_GROW) && wide_cap > slots_cap)
+            n = std::max(n, fig_wide_chunk(FigWide{FIG_WIDE_GROW, slots_cap, wide_cap}, 1, ctl[g].last, wide_cap, range - j, 1, 0));
         total += n;
         R.entries.push_back(FigEntry{g, n, 0, 0});
     }
+    if ((wide_mode & FIG_WIDE_IDLE) && wide_cap > slots_cap && (int)R.entries.size() == R.n_active) {
+        long long spare = (long long)(capacity / std::max(1, nsplit)) - total;      // workgroups of the lane's share this round leaves without an item
+        for (FigEntry &en : R.entries) {
+            const int j = ctl[en.gap].j, left = ctl[en.gap].range - j;
+            if (spare <= 0) break;
+            if (j == 0 || en.n == 0) continue;
+            const int n = fig_wide_chunk(FigWide{FIG_WIDE_IDLE, slots_cap, wide_cap}, en.n, en.n, wide_cap, left, 1, (int)std::min<long long>(en.n + spare, wide_cap));
+            if (n > en.n) { spare -= n - en.n; total += n - en.n; en.n = n; }
+        }
+    }
+    for (const FigEntry &en : R.entries) R.chunk = std::max(R.chunk, en.n);
     // items gap-major in descending-cost gap order (longest processing time first keeps the round's tail short)
     for (const FigEntry &en : R.entries)
         for (int k = en.n - 1; k >= 0; k--) R.items.push_back(FigItem{en.gap, ctl[en.gap].j + k, k, 0});
@@ -302,10 +341,19 @@ static int fig_round_stamp(FigRound &R, const FigGapCtl *ctl) {
 // Entries of a lane's continuation array: enough for every gap of `ids` to go through its whole range within one launch in chunks
 // of `minc` (FIG_MIN_CHUNK as it stands at upload), plus the end item and the last short chunk.  A fill with a smaller
 // FIG_MIN_CHUNK may find the array full; the gap is then left to the host's next round.
+// (Wide chunks only make a gap's chunks fewer.)
 static int fig_cont_capacity(const std::vector<int> &ids, const std::vector<FigDevGap> &gaps, int minc) {
     long long n = 0;
     for (int g : ids) n += gaps[(size_t)g].rangeCap / std::max(1, minc) + 3;
     return (int)std::min<long long>(std::max<long long>(n, 1), FIG_CONT_CAP_MAX);
+}
+
+// Items / entries a lane's buffers hold: a round has at most one chunk per gap, a chunk at most the gap's slots; one more
+// record per gap for the entries and the end list.
+static size_t fig_lane_items(const std::vector<int> &ids, const std::vector<FigDevGap> &gaps) {
+    size_t n = 0;
+    for (int g : ids) n += (size_t)gaps[(size_t)g].nslots + 1;
+    return std::max<size_t>(n, 1);
 }
 
 #endif

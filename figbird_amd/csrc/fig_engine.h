@@ -305,7 +305,8 @@ FIG_D void fig_eng_ident(FigEng &E, unsigned tid, unsigned nt, unsigned wsz) {
 
 // What a launch hands its workgroups besides model and batch: the class's capacities and memory form, the queue range.
 struct FigKernArgs { int capG, capGl, ncolE, Wcap, nteams, q_begin, q_end, qsel, tiles, tile_step, tile_cols, tiled_max, sh_on;
-                     int cont = 0, minc = 16, cont_live = 100, cont_prio = 1; };   // continuous form of the eval launch (FigKnobs, fig_abi_host.h)
+                     int cont = 0, minc = 16, cont_live = 100, cont_prio = 1;      // continuous form of the eval launch (FigKnobs, fig_abi_host.h)
+                     int wide = 0, wide_base = 64, wide_cap = 64; };               // its wide chunks: FIG_WIDE bits, base slots, wide cap (FigWide, fig_engine_sched.h)
 
 // LDS / slab carve-up of a workgroup (doubles first so everything stays 8-byte aligned):
 //   LDS table:  PQ[4][ncolE] (16 B each)  Q4[ncolE]  wbuf[nteams][Wcap]  | FigState  gs[capGl]  rb[FIG_MAX_READLEN+8]  plb

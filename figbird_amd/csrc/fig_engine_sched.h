@@ -81,6 +81,7 @@ FIG_D void fig_gap_begin(FigEng &E) {
         L.fill_or_not = 0; L.same_count = 0; L.same_thresh = M.unmapped ? 50 : 4; L.stuckCount = 0;
         int range = gapMax - gapMin + 1;
         if (range > E.B->capC) range = E.B->capC;        // host sizes capC from the same formula; defensive
+        if (range > g.rangeCap) range = g.rangeCap;      // the gap's own count from the same formula (fig_pack.h): its slab holds rangeCap records and min(rangeCap, W) slots; defensive
         L.range = range; L.side_flag = 0; L.less_read_flag = 0;
         L.prev_best = -1; L.curr_best = 0; L.prev_u = -1; L.curr_u = 0; L.sec_same = 0; L.sec_same2 = 0;
         L.done = 0; L.need_orig = 0; L.ev_iters = 0; L.ev_side_break = 0; L.ev_fill = 0;
@@ -499,10 +500,10 @@ FIG_D void fig_item_gap(FigEng &E, const FigScr &work, int gi, FigPersist &P) {
 
 // the gap's control word; publish: where its candidate loop stands, for the planner
 FIG_D FigGapCtl &fig_ctl_of(const FigEng &E, int gi) { return *(E.B->gapctl + gi); }
-FIG_D void fig_ctl_publish(const FigEng &E, int gi) {
+FIG_D void fig_ctl_publish(const FigEng &E, int gi, int last) {
     if (E.tid != 0) return;
     FigGapCtl &c = fig_ctl_of(E, gi);
-    c.status = E.S->L.done ? FIG_GAP_LOOP_DONE : FIG_GAP_MORE; c.j = E.S->L.j; c.range = E.S->L.range;
+    c.status = E.S->L.done ? FIG_GAP_LOOP_DONE : FIG_GAP_MORE; c.j = E.S->L.j; c.range = E.S->L.range; c.last = last;
 }
 
 // sequential mode: the whole gap
@@ -523,7 +524,7 @@ FIG_D void fig_item_begin(FigEng &E, const FigScr &work, int gi) {
         if (E.tid == 0) fig_ctl_of(E, gi).status = FIG_GAP_FINISHED;
     } else {
         fig_state_save(E, P);
-        fig_ctl_publish(E, gi);
+        fig_ctl_publish(E, gi, 0);
     }
     FIG_SYNC();
 }
@@ -551,7 +552,7 @@ FIG_D void fig_item_replay(FigEng &E, const FigScr &work, const FigEntry &en) {
     E.g = &E.B->gaps[en.gap];
     FigPersist P; fig_persist_of(*E.B, *E.g, P);
     fig_spec_replay(E, work, P, en.n, E.g->capGg);
-    fig_ctl_publish(E, en.gap);
+    fig_ctl_publish(E, en.gap, en.n);
 }
 
 // fallbacks + finalize + output of a gap whose loop is done
@@ -578,19 +579,52 @@ FIG_HD int fig_cont_chunk(int minc, int last, int slots, int left) {
     return n;
 }
 
+// Wide chunks (FIG_WIDE, FigKnobs): a gap that keeps running gets wider chunks than the `base` slots a gap has had so far, up to
+// the wide cap W (FIG_SLOTS_WIDE) and the min(rangeCap, W) slots its slab holds.  The one rule, for the kernel, the host planner
+// and the emulation.  It speaks of a gap's CONTINUED chunks only: the first one is the planner's as ever.
+//   today = fig_cont_chunk within the base slots: what the gap gets with `mode` 0 or after a chunk that was not consumed to
+//           its end (consumed_all = 0; the replay left something other than FIG_GAP_MORE);
+//   grow  (FIG_WIDE_GROW): up to twice the gap's last chunk -- a gap that ran 64 and then 128 candidates without a stop is the
+//           kind that runs on, and one that stops in the grown chunk has wasted at most about what it had already used;
+//   idle  (FIG_WIDE_IDLE): up to `spare`, the workgroups that would otherwise find nothing to do.
+// Neither ever makes the chunk smaller than `today`, and nothing goes past W, the gap's slots or what it has left.
+enum { FIG_WIDE_GROW = 1, FIG_WIDE_IDLE = 2 };
+struct FigWide { int mode, base, W; };               // FIG_WIDE bits; slots of a gap without it (64); the wide cap
+FIG_HD int fig_wide_chunk(FigWide w, int minc, int last, int slots, int left, int consumed_all, int spare) {
+    const int today = fig_cont_chunk(minc, last, slots < w.base ? slots : w.base, left);
+    if (!w.mode || !consumed_all) return today;
+    int cap = w.W < slots ? w.W : slots;
+    if (cap > left) cap = left;
+    int n = today;
+    if (w.mode & FIG_WIDE_GROW) { const int g = last > (1 << 29) ? (1 << 30) : 2 * last; const int c = g < cap ? g : cap; if (c > n) n = c; }
+    if (w.mode & FIG_WIDE_IDLE) { const int c = spare < cap ? spare : cap; if (c > n) n = c; }
+    return n;
+}
+
+// Chunks a gap with `left` candidates still needs when its next chunk is n and none of them stops it (nothing idle assumed):
+// FigCont::rank.  At most `left` trips.
+FIG_HD int fig_wide_rank(FigWide w, int minc, int n, int slots, int left) {
+    int r = 0;
+    const int trips = left;
+    for (int i = 0; i < trips && left > 0 && n > 0; i++) { r++; left -= n; n = fig_wide_chunk(w, minc, n, slots, left, 1, 0); }
+    return r;
+}
+
 // After the last item of the gap's chunk of n candidates: the replay, then `next` = the gap's next chunk or its end item.
-// FigCont::rank orders the published continuations: chunks the gap's candidate loop may still need, this one included (the
-// longest chain of chunks is the critical path of a lane); 1 for an end item.
-FIG_D void fig_item_continue(FigEng &E, const FigScr &work, int gi, int n, int minc, FigCont &next) {
+// FigCont::rank orders the published continuations: chunks the gap's candidate loop may still need under the rule in force, this
+// one included (the longest chain of chunks is the critical path of a lane); 1 for an end item.  next.pad: the chunk without
+// the widening (fig_cont_publish narrows a chunk the launch can no longer take, but never below that).
+FIG_D void fig_item_continue(FigEng &E, const FigScr &work, int gi, int n, int minc, FigWide w, int spare, FigCont &next) {
     fig_item_replay(E, work, FigEntry{gi, n, 0, 0});
     FIG_SYNC();
     const FigLoop &L = E.S->L;                    // (fig_spec_replay leaves the replayed state in place)
     next.gap = gi; next.next = 0; next.ready = 0; next.pad = 0;
     if (L.done) { next.kind = FIG_CONT_END; next.j0 = 0; next.n = 1; next.rank = 1; }
     else {
-        const int left = L.range - L.j;
-        next.kind = FIG_CONT_EVAL; next.j0 = L.j; next.n = fig_cont_chunk(minc, n, E.g->nslots, left);
-        next.rank = (left + next.n - 1) / (next.n > 0 ? next.n : 1);
+        const int left = L.range - L.j, slots = E.g->nslots;      // (not done: the replay consumed all n candidates of the chunk)
+        next.kind = FIG_CONT_EVAL; next.j0 = L.j; next.n = fig_wide_chunk(w, minc, n, slots, left, 1, spare);
+        next.pad = fig_wide_chunk(FigWide{0, w.base, w.W}, minc, n, slots, left, 1, 0);
+        next.rank = fig_wide_rank(w, minc, next.n, slots, left);
     }
     FIG_SYNC();
 }

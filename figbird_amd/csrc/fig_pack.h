@@ -79,12 +79,27 @@ struct FigPacked {
     bool ot_given = false;            // the caller supplied it; otherwise the library measures it (one process, batch order)
     int capR = 1, capP = 1, capC = 1, capG = 8, capW = 0, capE = 0;
     int64_t str_total = 0, n_gaps = 0, persist_total = 0, stream_total = 0;   // stream_total: dwords of the operand-select stream
-    int nslots = 64;                  // speculative candidate slots per gap (fig_engine_sched.h)
+    int nslots = 64;                  // speculative candidate slots of a gap's chunk unless it is widened: the base width (fig_engine_sched.h)
+    int nslots_wide = 64;             // W, the wide cap (FIG_SLOTS_WIDE, FigKnobs): a gap owns min(rangeCap, W) slots; set before fig_pack, never below the base width the planner is given
     int64_t packed_bytes() const {
         return (int64_t)(packed.size() * 4 + flank.size() + gaps.size() * sizeof(FigDevGap) + qual.size() +
                          (u_pos.size() * 3 + p_pos.size() * 5) * 4 + (u_woff.size() + p_woff.size() + p_qoff.size()) * 8);
     }
 };
+
+// Per-gap persistent slabs of the candidate-parallel scheduler, for the wide cap K.nslots_wide as it stands (fig_batch_upload
+// calls this again with a smaller one when the slab does not fit): FigDevGap::nslots, persistOff and K.persist_total.  A gap's
+// candidate loop never has more than rangeCap candidates (fig_gap_begin takes its range from the same formula and clamps to
+// it), so a gap of one candidate owns one slot; slot indices are below min(chunk, range - j) <= min(W, rangeCap).
+static void fig_pack_persist(FigPacked &K, size_t state_bytes) {
+    long long off = 0;
+    for (FigDevGap &d : K.gaps) {
+        d.nslots = std::max(1, std::min(d.rangeCap, K.nslots_wide));
+        d.persistOff = off;
+        off += (fig_persist_layout(nullptr, d.capGg, d.nU, d.nP, d.rangeCap, d.nslots, state_bytes, nullptr) + 255) & ~255LL;
+    }
+    K.persist_total = off;
+}
 
 // lds_fixed = bytes of LDS the kernel needs besides P/Q and the weight buffer, as a function of capG.
 static int fig_pack(const fig_model *m, const fig_gap_batch *b, size_t state_bytes, FigPacked &K) {
@@ -203,18 +218,9 @@ static int fig_pack(const fig_model *m, const fig_gap_batch *b, size_t state_byt
         int gm = std::max(d.G0, (int)(d.G0 * d.gpf2));
         if (m->unmapped_flag && d.G0 <= m->unm_limit) gm = std::max(gm, d.G0 < 30 ? 70 : 3 * d.G0);
         gmax[g] = std::min(gm, d.alloc_arg);
+        K.gaps[g].capGg = (gmax[g] + 7) & ~7; K.gaps[g].rangeCap = gap_range(d.G0, d.gpf1, d.gpf2);
     }
-    // per-gap persistent slabs of the candidate-parallel scheduler
-    {
-        long long off = 0;
-        for (int64_t g = 0; g < ng; g++) {
-            FigDevGap &d = K.gaps[g];
-            d.capGg = (gmax[g] + 7) & ~7; d.rangeCap = gap_range(d.G0, d.gpf1, d.gpf2); d.nslots = K.nslots;
-            d.persistOff = off;
-            off += (fig_persist_layout(nullptr, d.capGg, d.nU, d.nP, d.rangeCap, d.nslots, state_bytes, nullptr) + 255) & ~255LL;
-        }
-        K.persist_total = off;
-    }
+    fig_pack_persist(K, state_bytes);
     struct ClsDef { int capGl, nt; };
     const ClsDef defs[] = {{448, 256}, {1216, 512}, {1600, 512}, {1 << 30, 512}};   // longest candidate (columns), threads
     K.order.clear(); K.classes.clear();

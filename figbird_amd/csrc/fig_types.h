@@ -28,7 +28,9 @@ enum { FIG_ORG_NONE = 0, FIG_ORG_FINAL = 1, FIG_ORG_ORIGINAL = 2, FIG_ORG_TIEBRE
 // Control word of one gap in the candidate-parallel scheduler: the begin and replay items publish it (fig_ctl_publish,
 // fig_engine_sched.h), the round planner (fig_abi_host.h) reads a snapshot of all of them.
 enum { FIG_GAP_FINISHED = 0, FIG_GAP_MORE = 1, FIG_GAP_LOOP_DONE = 2 };   // output written ; candidates left to evaluate ; loop over, the end item is due
-struct FigGapCtl { int32_t status, j, range, reach; };                    // FIG_GAP_*, next candidate index, candidate count, reach bit of the probe item
+// FIG_GAP_*, next candidate index, candidate count; then the reach bit of the probe item (the pre-pass), or, in a fill, the size
+// of the chunk the gap's last replay went through (0 after the begin item): what the growth rule doubles (fig_wide_chunk)
+struct FigGapCtl { int32_t status, j, range; union { int32_t reach; int32_t last; }; };
 
 // Work items of a round, as the planner lays them out and the kernels read them (one 16-byte load each)
 struct alignas(16) FigItem { int32_t gap, j, slot, chunk; };               // evaluate candidate j of the gap into slot; chunk: see below
@@ -42,8 +44,9 @@ static_assert(sizeof(FigGapCtl) == 16 && sizeof(FigItem) == 16 && sizeof(FigEntr
 enum { FIG_CONT_EVAL = 0, FIG_CONT_END = 1 };
 #define FIG_CONT_CAP_MAX 65535       // entries of a lane's array at most: the scan's keys hold an entry's index in 16 bits
 struct alignas(16) FigCont { int32_t gap, j0, n, kind; int32_t next, ready, rank, pad; };
-// Header of a lane's continuation array (the entries follow it): entries reserved so far; workgroups of the launch that have left.  Zeroed, entries included, before every eval launch
-struct alignas(16) FigContHdr { int32_t tail, exited, pad[2]; };
+// Header of a lane's continuation array (the entries follow it): entries reserved so far; workgroups of the launch that have left;
+// published items nobody has claimed yet (idle-driven widening reads it; approximate by design, an item takes 100-500 ms).  Zeroed, entries included, before every eval launch
+struct alignas(16) FigContHdr { int32_t tail, exited, open, pad; };
 static_assert(sizeof(FigCont) == 32 && sizeof(FigContHdr) == 16, "continuation records: buffers are sized by sizeof");
 
 enum FigCounter {                    // slots of FigDevBatch::counters
@@ -51,6 +54,7 @@ enum FigCounter {                    // slots of FigDevBatch::counters
     FIG_CNT_FLOPS = 1, FIG_CNT_SPEC = 2,         // algorithmic flops: useful work only ; every speculative evaluation executed, discarded ones included
     FIG_CNT_MLE_ALG = 3, FIG_CNT_MLE_EXEC = 4,   // MLE passes: flops credited ; FP64 multiplies executed after pruning (raw totals, only their ratio is reported)
     FIG_CNT_CONT = 5,                // chunks continued inside an eval launch (continuous form)
+    FIG_CNT_NARROW = 6,              // of them, widened chunks published narrower because the launch was emptying (FIG_SCHED_LOG reports it)
     // FIG_PROF build: FigEng::prof[i] is counter PROF_LO + i below FIG_PROF_SPLIT, PROF_HI + (i - FIG_PROF_SPLIT) from it on; cycles in barriers; wave-cycles
     FIG_CNT_PROF_LO = 8, FIG_CNT_WAIT = 30, FIG_CNT_WAVE = 31, FIG_CNT_PROF_HI = 32,
     FIG_CNT_N = 64

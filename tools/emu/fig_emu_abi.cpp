@@ -48,6 +48,13 @@ extern "C" int fig_ctx_set_model(fig_ctx *ctx, const fig_model *m) {
 extern "C" int fig_batch_upload(fig_ctx *ctx, const fig_gap_batch *b) {
     if (!ctx || !b || !ctx->have_model) return FIG_EINVAL;
     ctx->K = FigPacked();
+    {   // the wide cap as the library takes it (no budget here: host memory), but never below THIS build's base width: FIG_EMU_CHUNK=<c>
+        // makes min(c, 64) the base (emu_run), so that a small FIG_SLOTS_WIDE lets small cases run into the cap
+        int base = ctx->K.nslots;
+        if (const char *ce = getenv("FIG_EMU_CHUNK")) base = std::min(std::max(1, atoi(ce)), base);
+        const FigKnobs kn = fig_knobs_from_env(ctx->hm.unmapped_flag);
+        ctx->K.nslots_wide = kn.wide ? std::max(base, std::min(kn.slots_wide, FIG_SLOTS_WIDE_MAX)) : base;      // wide slots only where the fill would widen, as in the library
+    }
     int rc = fig_pack(&ctx->hm, b, sizeof(FigState), ctx->K);
     if (rc) return rc;
     ctx->have_batch = true;
@@ -143,13 +150,17 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
             // Knobs as in the library, with a stand-in of 8 resident workgroups for the device's capacity: small enough that
             // the admission cut-off leaves gaps waiting in batches of a few dozen gaps.  Results do not depend on it, nor on
             // the chunk -- that is the invariant under test.  FIG_EMU_CHUNK=<n>: exactly min(n, nslots, range - j)
-            // candidates per admitted gap and round.
-            int minc = knobs.minc, slots_cap = K.nslots;
-            if (const char *ce = getenv("FIG_EMU_CHUNK")) { minc = std::max(1, atoi(ce)); slots_cap = std::min(minc, K.nslots); }
+            // candidates per admitted gap and round.  Wide chunks (FIG_WIDE): the rule of fig_wide_chunk on top, with these base
+            // slots and FIG_SLOTS_WIDE as at upload; under FIG_EMU_CHUNK only when FIG_WIDE is set explicitly (the sizes stay
+            // fixed otherwise).  The one workgroup here is never idle: `spare` is 0.
+            int minc = knobs.minc, slots_cap = K.nslots, wide = knobs.wide;
+            if (const char *ce = getenv("FIG_EMU_CHUNK")) { minc = std::max(1, atoi(ce)); slots_cap = std::min(minc, K.nslots); if (!getenv("FIG_WIDE")) wide = 0; }
+            slots_cap = std::min(slots_cap, K.nslots_wide);      // (a batch uploaded under a smaller FIG_EMU_CHUNK than this fill's)
             FigRound R;
             int n_active_max = 0;
             while (true) {
-                fig_plan_round(ids, ctl.data(), 8, c.nsplit, slots_cap, minc, knobs.ipw, n_active_max, R);
+                fig_plan_round(ids, ctl.data(), 8, c.nsplit, slots_cap, wide, K.nslots_wide, knobs.wide_max_active, minc, knobs.ipw, n_active_max, R);
+                const FigWide fw{fig_wide_for_lane(wide, n_active_max, knobs.wide_max_active), slots_cap, K.nslots_wide};
                 if (!R.n_active) break;
                 if (!knobs.cont) {       // FIG_SCHED=rounds: all items of the round, then all replays
                     for (const FigItem &it : R.items) { poison(); fig_item_eval<true>(E, work, it); }      // every item starts from poisoned scratch + LDS
@@ -165,7 +176,7 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
                     if (en.n == 0) { poison(); fig_item_replay(E, work, en); continue; }      // (the replay kernel's share)
                     FigCont nx; nx.n = en.n;
                     while (true) {
-                        poison(); fig_item_continue(E, work, en.gap, nx.n, minc, nx);
+                        poison(); fig_item_continue(E, work, en.gap, nx.n, minc, fw, 0, nx);
                         if (nx.kind == FIG_CONT_END) { poison(); fig_item_end<true>(E, work, nx.gap); break; }
                         counters[FIG_CNT_CONT]++;
                         for (int k = nx.n - 1; k >= 0; k--) { poison(); fig_item_eval<true>(E, work, FigItem{nx.gap, nx.j0 + k, k, nx.n}); }
@@ -186,10 +197,18 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
 
 // Test-only view of the round planner (tests/test_abi_and_host.py): one round on a hand-made gapctl snapshot.  items /
 // entries take up to cap_ints ints each; returns n_active, or -1 when they do not fit.
+extern "C" int fig_emu_plan_round_wide(const int *ids, int n_ids, const int32_t *ctl, int capacity, int nsplit, int slots_cap, int wide_mode, int wide_cap, int wide_max_active, int minc, double ipw,
+                                       int *n_active_max, int *items, int *n_items, int *entries, int *n_entries, int cap_ints, int *chunk);
 extern "C" int fig_emu_plan_round(const int *ids, int n_ids, const int32_t *ctl, int capacity, int nsplit, int slots_cap, int minc, double ipw,
                                   int *n_active_max, int *items, int *n_items, int *entries, int *n_entries, int cap_ints, int *chunk) {
+    return fig_emu_plan_round_wide(ids, n_ids, ctl, capacity, nsplit, slots_cap, 0, slots_cap, 0, minc, ipw, n_active_max, items, n_items, entries, n_entries, cap_ints, chunk);      // (its slots_cap is both caps: a hard one)
+}
+
+// The same with the wide cap and the FIG_WIDE bits of its own (tests/test_wide_chunks.py); the fourth int32 of a ctl row is FigGapCtl::last.
+extern "C" int fig_emu_plan_round_wide(const int *ids, int n_ids, const int32_t *ctl, int capacity, int nsplit, int slots_cap, int wide_mode, int wide_cap, int wide_max_active, int minc, double ipw,
+                                       int *n_active_max, int *items, int *n_items, int *entries, int *n_entries, int cap_ints, int *chunk) {
     FigRound R;
-    fig_plan_round(std::vector<int>(ids, ids + n_ids), (const FigGapCtl *)ctl, capacity, nsplit, slots_cap, minc, ipw, *n_active_max, R);   // (rows of four int32, as FigGapCtl is)
+    fig_plan_round(std::vector<int>(ids, ids + n_ids), (const FigGapCtl *)ctl, capacity, nsplit, slots_cap, wide_mode, wide_cap, wide_max_active, minc, ipw, *n_active_max, R);   // (rows of four int32, as FigGapCtl is)
     if ((int)R.items.size() * 4 > cap_ints || (int)R.entries.size() * 4 > cap_ints) return -1;
     memcpy(items, R.items.data(), R.items.size() * sizeof(FigItem)); memcpy(entries, R.entries.data(), R.entries.size() * sizeof(FigEntry));
     *n_items = (int)R.items.size(); *n_entries = (int)R.entries.size(); *chunk = R.chunk;
@@ -197,3 +216,10 @@ extern "C" int fig_emu_plan_round(const int *ids, int n_ids, const int32_t *ctl,
 }
 
 extern "C" int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) { return fig_fill_gaps_once(ctx, batch, out); }
+
+// Test-only views of the chunk functions of fig_engine_sched.h (tests/test_wide_chunks.py)
+extern "C" int fig_emu_cont_chunk(int minc, int last, int slots, int left) { return fig_cont_chunk(minc, last, slots, left); }
+extern "C" int fig_emu_wide_chunk(int mode, int minc, int last, int base, int W, int slots, int left, int consumed_all, int spare) {
+    return fig_wide_chunk(FigWide{mode, base, W}, minc, last, slots, left, consumed_all, spare);
+}
+extern "C" int fig_emu_wide_rank(int mode, int minc, int n, int base, int W, int slots, int left) { return fig_wide_rank(FigWide{mode, base, W}, minc, n, slots, left); }
