@@ -143,6 +143,72 @@ class Indel:
     state: np.ndarray
 
 
+class FigGapPolish(C.Structure):
+    _fields_ = [("edit", c_i32_p), ("edit_end", c_i32_p), ("polished_len", c_i32_p), ("draw_pos", c_i32_p), ("n_ins", c_i32_p), ("n_del", c_i32_p),
+                ("rounds", c_i32_p), ("ll_before", c_double_p), ("ll_after", c_double_p), ("state", c_u8_p)]
+
+
+# fig_gap_polish::state bits and the limits of the loop (include/figbird_hip.h)
+POLISH_ON, POLISH_EDITED, POLISH_REJECTED, POLISH_REVERTED, POLISH_CAPPED = 1, 2, 4, 8, 16
+POLISH_MAX_SITES, POLISH_MAX_ROUNDS, POLISH_DEFAULT_ROUNDS = 16, 8, 4
+
+
+def polish_string(edit, edit_end: int, string) -> np.ndarray:
+    """the polished string of one gap (uint8) from its original bytes and its edit words: the inserted bases of edit[x], then
+    string[x] unless removed; then the bases of edit_end"""
+    out = bytearray()
+    for w, ch in list(zip(edit, string)) + [(edit_end, None)]:
+        w = int(w)
+        out += bytes(b"ACGT"[(w >> (4 + 2 * i)) & 3] for i in range((w >> 1) & 7))
+        if ch is not None and not w & 1:
+            out.append(int(ch))
+    return np.frombuffer(bytes(out), dtype=np.uint8)
+
+
+@dataclass
+class Polish:
+    """fig_gap_polish of one call: edit is indexed like the strings (column x of gap g at str_off[g] + x), draw_pos like the unmapped
+    part of the draw plane, everything else per gap.  filled: the FillResult the call was given."""
+    edit: np.ndarray
+    edit_end: np.ndarray
+    polished_len: np.ndarray
+    draw_pos: np.ndarray
+    n_ins: np.ndarray
+    n_del: np.ndarray
+    rounds: np.ndarray
+    ll_before: np.ndarray
+    ll_after: np.ndarray
+    state: np.ndarray
+    filled: Optional["FillResult"] = None
+
+    def strings(self):
+        """the polished string of every gap (uint8 arrays); a gap that is off keeps its own bytes"""
+        f = self.filled
+        out = []
+        for g in range(len(self.state)):
+            a = int(f.str_off[g]); n = max(int(f.filled_len[g]), 0)
+            own = np.asarray(f.raw[a:a + n], dtype=np.uint8)
+            out.append(polish_string(self.edit[a:a + n], int(self.edit_end[g]), own) if self.state[g] & POLISH_ON else own)
+        return out
+
+    def result(self) -> "FillResult":
+        """a FillResult made by hand of the polished strings, the shifted offsets and the draw planes: it goes straight into
+        quality(), placement() or indel() while the batch is resident"""
+        f = self.filled
+        strs = self.strings()
+        n = len(strs)
+        fl = np.array(f.filled_len[:n], dtype=np.int32)
+        dpos, disz, dlen = (np.array(a, dtype=np.int32) for a in f.draw)
+        for g in range(n):
+            if self.state[g] & POLISH_ON:
+                fl[g] = len(strs[g]); dlen[2 * g] = len(strs[g])
+        so = np.concatenate([[0], np.cumsum([len(s) for s in strs])]).astype(np.int64)
+        raw = np.concatenate(strs + [np.zeros(0, np.uint8)]).astype(np.uint8)
+        dpos[:len(self.draw_pos)] = self.draw_pos
+        return FillResult(fl, np.array(f.gaptofill[:n]), None, str_off=so, raw=raw if len(raw) else np.zeros(1, np.uint8), draw=(dpos, disz, dlen),
+                          support_origin=f.support_origin)
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -153,7 +219,7 @@ class FigStats(C.Structure):
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
            "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
            "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality", "fig_batch_placement",
-           "fig_batch_softqual", "fig_batch_indel"]
+           "fig_batch_softqual", "fig_batch_indel", "fig_batch_polish", "fig_polish_apply"]
 
 _lib = None
 _host = None
@@ -195,6 +261,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.fig_batch_softqual.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigReadPlacement), C.POINTER(FigGapSoftqual)]
     if hasattr(lib, "fig_batch_indel"):               # (likewise)
         lib.fig_batch_indel.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigGapIndel)]
+    if hasattr(lib, "fig_batch_polish"):              # (likewise)
+        lib.fig_batch_polish.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.c_int, C.POINTER(FigGapPolish)]
+        lib.fig_polish_apply.argtypes = [C.POINTER(FigGapResults), C.POINTER(FigGapPolish), C.c_int64, c_u8_p]
     if path is None:
         _lib = lib
     return lib
@@ -241,6 +310,17 @@ def load_host_library() -> C.CDLL:
         _host.fighost_indel_call.argtypes = [C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
         _host.fighost_indel_call_end.argtypes = [C.c_int32, C.c_int32]
         _host.fighost_run_write_indel.argtypes = [C.c_void_p, c_i32_p, c_i64_p, C.c_char_p, C.c_char_p, c_u8_p, C.c_char_p, C.c_int]
+        _host.fighost_polish_shift.argtypes = [C.c_int32, C.c_int, C.c_int32]
+        _host.fighost_polish_touched.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        _host.fighost_polish_counted.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_int32]
+        _host.fighost_polish_sites.argtypes = [C.c_char_p, C.c_int32, C.c_char, c_i32_p, c_i32_p]
+        _host.fighost_polish_best.argtypes = [c_double_p, C.c_int]
+        _host.fighost_polish_accept.argtypes = [C.c_double, C.c_double]
+        _host.fighost_polish_keep.argtypes = [C.c_double, C.c_double]
+        _host.fighost_polish_insert.argtypes = [c_i32_p, C.c_int32, c_i32_p, C.c_int64, C.c_int]
+        _host.fighost_polish_remove.argtypes = [c_i32_p, C.c_int32, c_i32_p, C.c_int64]
+        _host.fig_polish_apply.argtypes = [C.POINTER(FigGapResults), C.POINTER(FigGapPolish), C.c_int64, c_u8_p]
+        _host.fighost_run_write_polished.argtypes = [C.c_void_p, c_i32_p, c_i64_p, C.c_char_p, c_i32_p, c_i32_p, c_i32_p, c_u8_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -388,6 +468,7 @@ class FillResult:
     placement: Optional["Placement"] = None   # fig_read_placement of the fill's drawn unmapped reads, when requested
     quality: Optional[tuple] = None        # (loglik float64 [total, 4], phred uint8 [total], state uint8 [n_gaps]) of fig_gap_quality, indexed like raw
     indel: Optional["Indel"] = None        # fig_gap_indel of the fill's strings and drawn unmapped reads, when requested
+    polish: Optional["Polish"] = None      # fig_gap_polish of the fill's strings and drawn unmapped reads, when requested
     softqual: Optional["SoftQual"] = None  # fig_gap_softqual of the fill's strings, when requested
 
     @property
@@ -556,6 +637,31 @@ class Engine:
         return Indel(d[0][:nu], d[1][:nu], ri[0][:nu], ri[1][:nu], ri[2][:nu], ri[3][:nu], pl[0][:total], pl[1][:total], pl[2][:total], ie[:n],
                      call[:total], ce[:n], stt[:n])
 
+    def polish(self, res: FillResult, origin: Optional[np.ndarray] = None, max_rounds: int = 0) -> "Polish":
+        """fig_batch_polish of the strings and draw planes in `res` against the resident batch; `origin` as for quality(); max_rounds
+        1..8, or 0 for the library's default.  The buffers handed to the library start as 0xFF bytes, so that an element it failed
+        to write shows.  `res` is not changed."""
+        self._need("fig_batch_polish", "polish")
+        r, keep = self._filled_struct("polish", res)
+        n, nu = self.n_gaps, self._n_ureads()
+        if len(keep[3]) < nu:
+            raise ValueError("polish: one drawn offset per unmapped read of the resident batch")
+        total = int(keep[1][n])
+        org, org_p = self._origin_arg("polish", origin)
+        m, t, gm = max(nu, 1), max(total, 1), max(n, 1)
+        ed = np.full(t, -1, dtype=np.int32); dp = np.full(m, -1, dtype=np.int32)
+        gi = [np.full(gm, -1, dtype=np.int32) for _ in range(5)]
+        d = [np.zeros(gm) for _ in range(2)]
+        for a in d:
+            a.view(np.uint8)[...] = 0xFF
+        stt = np.full(gm, 0xFF, dtype=np.uint8)
+        gp = FigGapPolish()
+        gp.edit = _p(ed, c_i32_p); gp.draw_pos = _p(dp, c_i32_p)
+        gp.edit_end, gp.polished_len, gp.n_ins, gp.n_del, gp.rounds = (_p(a, c_i32_p) for a in gi)
+        gp.ll_before = _p(d[0], c_double_p); gp.ll_after = _p(d[1], c_double_p); gp.state = _p(stt, c_u8_p)
+        self._check(self.lib.fig_batch_polish(self.ctx, C.byref(r), org_p, int(max_rounds), C.byref(gp)), "fig_batch_polish")
+        return Polish(ed[:total], gi[0][:n], gi[1][:n], dp[:nu], gi[2][:n], gi[3][:n], gi[4][:n], d[0][:n], d[1][:n], stt[:n], filled=res)
+
     def quality(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: Optional["Placement"] = None, min_pq: Optional[int] = None):
         """fig_batch_quality of the strings and draw planes in `res` against the resident batch; `origin` is
         FillResult.support_origin, or None for no origin test.  Returns (loglik [total, 4], phred [total], state [n_gaps]) with
@@ -581,8 +687,11 @@ class Engine:
         self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), org_p, C.byref(gq)), "fig_batch_quality")
         return ll[:total], ph[:total], stt[:n]
 
-    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False, indel: bool = False):
-        """quality, placement, softqual and indel need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False, indel: bool = False, polish: bool = False):
+        """quality, placement, softqual, indel and polish need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+        if polish:
+            self._need("fig_batch_polish", "polish=True")
+            draw = support = True
         if quality:
             self._need("fig_batch_quality", "quality=True")
         if placement:
@@ -618,11 +727,12 @@ class Engine:
         return plc, qual, (self.softqual(filled, filled.support_origin) if softqual else None), (self.indel(filled, filled.support_origin) if indel else None)
 
     def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-                      placement: bool = False, softqual: bool = False, indel: bool = False) -> FillResult:
+                      placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False) -> FillResult:
         """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins);
         placement=True likewise fills FillResult.placement (fig_batch_placement with the origins), softqual=True
-        FillResult.softqual (fig_batch_softqual with the origins), indel=True FillResult.indel (fig_batch_indel with the origins)."""
-        draw, support = self._implied(support, draw, quality, placement, softqual, indel)
+        FillResult.softqual (fig_batch_softqual with the origins), indel=True FillResult.indel (fig_batch_indel with the origins),
+        polish=True FillResult.polish (fig_batch_polish with the origins)."""
+        draw, support = self._implied(support, draw, quality, placement, softqual, indel, polish)
         n = self.n_gaps
         nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1]) if draw else None
         r, fl, gt, so, st, planes = self._result_arrays(n, self.cap, nr, draw)
@@ -658,6 +768,8 @@ class Engine:
         if support:
             res.support = sup_c[:int(so[n])]; res.support_origin = sup_o[:n]
         res.placement, res.quality, res.softqual, res.indel = self._post_fill(res, placement, quality, softqual=softqual, indel=indel)
+        if polish:
+            res.polish = self.polish(res, res.support_origin)
         return res
 
     def free_batch(self):
@@ -687,7 +799,8 @@ class Engine:
             self._check(self.lib.fig_batch_upload(self.ctx, C.byref(cbatch)), "fig_batch_upload")
 
     def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False, quality: bool = False,
-                    keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None, softqual: bool = False, indel: bool = False) -> FillResult:
+                    keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None, softqual: bool = False, indel: bool = False,
+                    polish: bool = False, polish_rounds: int = 0) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
         resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
@@ -695,10 +808,10 @@ class Engine:
         fig_batch_quality before the batch is freed (field `quality`).  keep_resident=True leaves an uploaded batch resident
         for a further call.  placement=True likewise runs fig_batch_placement (field `placement`); with min_pq as well the
         quality leaves out the scored reads below that pq (Engine.quality).  softqual=True likewise runs fig_batch_softqual (field
-        `softqual`), indel=True fig_batch_indel (field `indel`)."""
-        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual, indel)
+        `softqual`), indel=True fig_batch_indel (field `indel`), polish=True fig_batch_polish with polish_rounds (field `polish`)."""
+        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual, indel, polish)
         placement = placement or min_pq is not None
-        qual = plc = sq = ind = None
+        qual = plc = sq = ind = pol = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         nr = n_ureads + n_preads
@@ -715,6 +828,9 @@ class Engine:
                 if placement or quality or softqual or indel:
                     self.n_gaps = n; self._cb = cbatch
                     plc, qual, sq, ind = self._post_fill(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), placement, quality, min_pq, softqual, indel)
+                if polish:
+                    self.n_gaps = n; self._cb = cbatch
+                    pol = self.polish(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), sup_o, polish_rounds)
             finally:
                 if not keep_resident:
                     self.lib.fig_batch_free(self.ctx)
@@ -735,13 +851,16 @@ class Engine:
         if indel:
             zi, zb = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8)
             res.indel = ind if ind is not None else Indel(np.zeros(0), np.zeros(0), zi, zi, zi, zi, zi, zi, zi, zi, zb, zb, zb)
+        if polish:
+            zi = np.zeros(0, dtype=np.int32)
+            res.polish = pol if pol is not None else Polish(zi, zi, zi, zi, zi, zi, zi, np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.uint8), filled=res)
         return res
 
     def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-             placement: bool = False, softqual: bool = False, indel: bool = False) -> FillResult:
+             placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual, indel)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual, indel, polish)
         finally:
             self.free_batch()
 

@@ -25,6 +25,7 @@
 #include "fig_placement.h"
 #include "fig_softqual.h"
 #include "fig_indel.h"
+#include "fig_polish.h"
 
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
@@ -1099,9 +1100,9 @@ extern "C" int fig_batch_softqual(fig_ctx *ctx, const fig_gap_results *f, const 
 
 // Indel evidence per filled base (fig_indel.h: the kernel and the path; fig_indel_host.h: tables, which gaps are on, which reads are
 // aligned, the call)
-extern "C" int fig_batch_indel(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_indel *out) {
-    if (!out || !out->ll_flat || !out->ll_gapped || !out->n_ins || !out->n_del || !out->d_end || !out->d_start || !out->del_reads || !out->ins_reads ||
-        !out->cover || !out->ins_end || !out->call || !out->call_end || !out->state) return FIG_EINVAL;
+struct FigIndelInfo { int64_t gaps_on = 0, reads = 0, events = 0, called = 0; float ms = 0; };
+// The pass itself, as fig_batch_indel and every round of fig_batch_polish run it: `out` has every member
+static int fig_indel_pass(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_indel *out, FigIndelInfo &info) {
     FigPostFill P;
     FIG_TRY(P.open(ctx, f));
     const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
@@ -1176,11 +1177,255 @@ extern "C" int fig_batch_indel(fig_ctx *ctx, const fig_gap_results *f, const int
             called += out->call_end[g] != '.';
         }
     }
-    if (fig_knobs_from_env(ctx->dm.unmapped).log)
-        fprintf(stderr, "[figindel] gaps on %lld of %lld, reads aligned %lld, reads with an event %lld, columns called %lld, kernel %.3f ms\n",
-                (long long)gaps_on, (long long)ng, (long long)reads, (long long)events, (long long)called, P.ms);
+    info.gaps_on = gaps_on; info.reads = reads; info.events = events; info.called = called; info.ms = P.ms;
     return FIG_OK;
 }
+static bool fig_indel_members(const fig_gap_indel *out) {
+    return out->ll_flat && out->ll_gapped && out->n_ins && out->n_del && out->d_end && out->d_start && out->del_reads && out->ins_reads &&
+           out->cover && out->ins_end && out->call && out->call_end && out->state;
+}
+extern "C" int fig_batch_indel(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_indel *out) {
+    if (!out || !fig_indel_members(out)) return FIG_EINVAL;
+    FigIndelInfo info;
+    FIG_TRY(fig_indel_pass(ctx, f, origin, out, info));
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figindel] gaps on %lld of %lld, reads aligned %lld, reads with an event %lld, columns called %lld, kernel %.3f ms\n",
+                (long long)info.gaps_on, (long long)ctx->n_gaps, (long long)info.reads, (long long)info.events, (long long)info.called, info.ms);
+    return FIG_OK;
+}
+
+// Polish of the filled strings (fig_polish.h: the scoring kernel; fig_polish_host.h: every rule of the loop and the edit planes).
+// The loop works on copies: per gap that is on its current string, the offsets of its reads, the latest pass's ll_gapped and calls.
+// Every round is one launch of the polish kernel over all gaps' candidates and one indel pass over all gaps' edited strings.
+extern "C" int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, int max_rounds, fig_gap_polish *out) {
+    if (!out || !out->edit || !out->edit_end || !out->polished_len || !out->draw_pos || !out->n_ins || !out->n_del || !out->rounds ||
+        !out->ll_before || !out->ll_after || !out->state) return FIG_EINVAL;
+    if (max_rounds < 0 || max_rounds > FIG_POLISH_MAX_ROUNDS) return FIG_EINVAL;
+    if (max_rounds == 0) max_rounds = FIG_POLISH_DEFAULT_ROUNDS;
+    FigPostFill P;
+    FIG_TRY(P.open(ctx, f));
+    const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
+    const FigDevBatch &db = ctx->db;
+    const int L = ctx->dm.L;
+    const size_t gm = (size_t)std::max<int64_t>(ng, 1), um = (size_t)std::max<int64_t>(nu, 1);
+    // the buffers of an indel pass; the first runs over the caller's strings and checks them as fig_batch_indel does
+    struct Pass {
+        std::vector<double> ll_flat, ll; std::vector<int32_t> ri, pl, ie; std::string call, call_end; std::vector<uint8_t> st;
+        fig_gap_indel gi;
+        void size(size_t um, size_t t, size_t gm) {
+            ll_flat.assign(um, 0.0); ll.assign(um, 0.0); ri.assign(um * 4, 0); pl.assign(std::max<size_t>(t, 1) * 3, 0); ie.assign(gm, 0);
+            call.assign(std::max<size_t>(t, 1), '.'); call_end.assign(gm, '.'); st.assign(gm, 0);
+            const size_t tt = std::max<size_t>(t, 1);
+            gi.ll_flat = ll_flat.data(); gi.ll_gapped = ll.data(); gi.n_ins = ri.data(); gi.n_del = ri.data() + um; gi.d_end = ri.data() + 2 * um; gi.d_start = ri.data() + 3 * um;
+            gi.del_reads = pl.data(); gi.ins_reads = pl.data() + tt; gi.cover = pl.data() + 2 * tt; gi.ins_end = ie.data();
+            gi.call = &call[0]; gi.call_end = &call_end[0]; gi.state = st.data();
+        }
+    } I;
+    I.size(um, (size_t)total, gm);
+    FigIndelInfo info;
+    float ms_indel = 0, ms_polish = 0;
+    FIG_TRY(fig_indel_pass(ctx, f, origin, &I.gi, info));
+    ms_indel += info.ms;
+    std::vector<int32_t> hlen(um, 0);
+    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+    for (int64_t r = 0; r < nu; r++) hlen[(size_t)r] = std::min(std::max(hlen[(size_t)r], 0), L);
+    // the working copies
+    std::vector<std::string> cur(gm), calls(gm);
+    std::vector<char> call_end(gm, '.');
+    std::vector<uint8_t> active(gm, 0);
+    std::vector<int32_t> wpos(um, INT32_MIN), wlen(gm, 0), wdl(2 * gm, -1);
+    std::vector<double> curll(I.ll);
+    const std::vector<double> ll0(I.ll);
+    if (nu > 0) memcpy(wpos.data(), f->draw_pos, (size_t)nu * sizeof(int32_t));
+    for (int64_t i = 0; i < total; i++) out->edit[i] = 0;
+    int64_t gaps_on = 0, n_sites = 0, n_cands = 0, n_acc = 0, n_rej = 0, n_rev = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        const bool on = I.st[(size_t)g] == FIG_INDEL_ON;
+        out->state[g] = on ? FIG_POLISH_ON : 0; out->edit_end[g] = 0; out->polished_len[g] = f->filled_len[g];
+        out->n_ins[g] = 0; out->n_del[g] = 0; out->rounds[g] = 0; out->ll_before[g] = 0.0; out->ll_after[g] = 0.0;
+        wlen[(size_t)g] = f->filled_len[g]; wdl[2 * (size_t)g] = f->draw_len[2 * g]; wdl[2 * (size_t)g + 1] = f->draw_len[2 * g + 1];
+        if (!on) continue;
+        gaps_on++; active[(size_t)g] = 1;
+        cur[(size_t)g].assign(f->str + f->str_off[g], (size_t)f->filled_len[g]);
+        calls[(size_t)g].assign(I.call, (size_t)f->str_off[g], (size_t)f->filled_len[g]);
+        call_end[(size_t)g] = I.call_end[(size_t)g];
+    }
+    std::vector<double> tid((size_t)(2 * L));
+    fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
+    std::vector<int64_t> wso((size_t)ng + 1, 0);
+    std::string wstr;
+    auto compact = [&] {                                          // the round's strings back to back: nothing for a gap that is off
+        wstr.clear();
+        for (int64_t g = 0; g < ng; g++) { wso[(size_t)g] = (int64_t)wstr.size(); if (out->state[g] & FIG_POLISH_ON) wstr += cur[(size_t)g]; }
+        wso[(size_t)ng] = (int64_t)wstr.size();
+        if (wstr.empty()) wstr.push_back('N');
+    };
+    struct Site { int32_t x, kind; int first, m; };               // its candidates are first .. first + m - 1
+    struct Saved { int64_t g; std::string str; std::vector<int32_t> pos, edit; int32_t edit_end; };
+    int rounds_run = 0;
+    for (int round = 1; round <= max_rounds; round++) {
+        std::vector<int32_t> cands, items;
+        std::vector<int64_t> cand_off;
+        std::vector<std::vector<Site>> sites(gm);
+        int64_t out_len = 0;
+        for (int64_t g = 0; g < ng; g++) {
+            if (!active[(size_t)g]) continue;
+            const int32_t n = (int32_t)cur[(size_t)g].size(), n0 = f->filled_len[g];
+            int32_t sx[FIG_POLISH_MAX_SITES], sk[FIG_POLISH_MAX_SITES];
+            const int m = fig_polish_sites(calls[(size_t)g].data(), n, call_end[(size_t)g], sx, sk);
+            if (m == 0) { active[(size_t)g] = 0; continue; }
+            out->rounds[g]++; n_sites += m;
+            const int64_t nU = P.hg[(size_t)g].nU;
+            for (int i = 0; i < m; i++) {
+                const bool can = sk[i] == FIG_POLISH_DEL ? n >= 2 : fig_polish_can_insert(out->edit + f->str_off[g], n0, out->edit_end[g], sx[i]);
+                if (!can) { out->state[g] |= FIG_POLISH_CAPPED; continue; }
+                const int nb = sk[i] == FIG_POLISH_DEL ? 1 : 4;
+                sites[(size_t)g].push_back({sx[i], sk[i], (int)cand_off.size(), nb});
+                for (int b = 0; b < nb; b++) {
+                    cands.push_back((int32_t)g); cands.push_back(sk[i]); cands.push_back(sx[i]); cands.push_back(b);
+                    cand_off.push_back(out_len); out_len += nU;
+                }
+            }
+            if (sites[(size_t)g].empty()) active[(size_t)g] = 0;
+        }
+        if (cands.empty()) break;
+        rounds_run++;
+        n_cands += (int64_t)cand_off.size();
+        if (cand_off.size() > (size_t)INT32_MAX / 4) return FIG_EUNSUP;
+        // a chunk with no counted read is no item
+        for (size_t c = 0; c < cand_off.size(); c++) {
+            const int64_t g = cands[4 * c], base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
+            const int32_t n = (int32_t)cur[(size_t)g].size();
+            for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {
+                bool any = false;
+                for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt) && !any; r++)
+                    any = fig_polish_counted(wpos[(size_t)(base + r)], hlen[(size_t)(base + r)], n, cands[4 * c + 1], cands[4 * c + 2]);
+                if (any) { items.push_back((int32_t)c); items.push_back((int32_t)c0); }
+            }
+        }
+        std::vector<double> sc((size_t)std::max<int64_t>(out_len, 1), 0.0);
+        if (!items.empty()) {
+            compact();
+            FigPostFill Q;                                        // the round's own device buffers
+            Q.ctx = ctx; Q.f = f;
+            std::vector<int32_t> ncol(gm, 0);
+            for (int64_t g = 0; g < ng; g++) if (out->state[g] & FIG_POLISH_ON) ncol[(size_t)g] = (int32_t)cur[(size_t)g].size();
+            FigPolishArgs A;
+            A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank; A.L = L;
+            A.draw_pos = Q.up(wpos.data(), (size_t)nu);
+            A.items = Q.up(items.data(), items.size());
+            A.cands = Q.up(cands.data(), cands.size());
+            A.cand_off = Q.up(cand_off.data(), cand_off.size());
+            A.ncol = Q.up(ncol.data(), (size_t)ng);
+            A.str_off = Q.up(wso.data(), (size_t)(ng + 1));
+            A.str = Q.up(wstr.data(), wstr.size());
+            A.tabs = Q.up(P.tabs.data(), P.tabs.size());
+            A.tabs_id = Q.up(tid.data(), tid.size());
+            A.out = (double *)Q.alloc((size_t)out_len * sizeof(double));
+            if (A.out) FIG_HIP(hipMemsetAsync(A.out, 0, (size_t)out_len * sizeof(double), ctx->stream));
+            FIG_TRY(Q.run([&] { fig_polish_launch(A, (unsigned)(items.size() / 2), ctx->stream); },
+                          [&] { return Q.fetch(sc.data(), A.out, (size_t)out_len * sizeof(double)); }));
+            ms_polish += Q.ms;
+        }
+        // best per site, accept, apply
+        std::vector<Saved> saved;
+        for (int64_t g = 0; g < ng; g++) {
+            if (sites[(size_t)g].empty()) continue;
+            const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU, s0 = f->str_off[g];
+            const int32_t n = (int32_t)cur[(size_t)g].size(), n0 = f->filled_len[g];
+            std::vector<std::pair<const Site *, int>> acc;        // the site and the base of its accepted candidate
+            for (const Site &s : sites[(size_t)g]) {
+                double T[4], T0 = 0.0;
+                for (int b = 0; b < s.m; b++) T[b] = 0.0;
+                for (int64_t r = 0; r < cnt; r++) {
+                    if (!fig_polish_counted(wpos[(size_t)(base + r)], hlen[(size_t)(base + r)], n, s.kind, s.x)) continue;
+                    T0 = T0 + curll[(size_t)(base + r)];
+                    for (int b = 0; b < s.m; b++) T[b] = T[b] + sc[(size_t)(cand_off[(size_t)(s.first + b)] + r)];
+                }
+                const int best = fig_polish_best(T, s.m);
+                if (fig_polish_accept(T[best], T0)) { acc.push_back({&s, best}); n_acc++; }
+                else { out->state[g] |= FIG_POLISH_REJECTED; n_rej++; }
+            }
+            if (acc.empty()) { active[(size_t)g] = 0; continue; }
+            saved.push_back({g, cur[(size_t)g], std::vector<int32_t>(wpos.begin() + base, wpos.begin() + base + cnt),
+                             std::vector<int32_t>(out->edit + s0, out->edit + s0 + n0), out->edit_end[g]});
+            int applied = 0;
+            for (size_t a = acc.size(); a-- > 0;) {               // right to left
+                const Site &s = *acc[a].first;
+                std::string &str = cur[(size_t)g];
+                if (s.kind == FIG_POLISH_DEL) {
+                    if (str.size() < 2) { out->state[g] |= FIG_POLISH_CAPPED; continue; }
+                    fig_polish_remove(out->edit + s0, n0, &out->edit_end[g], s.x);
+                    str.erase((size_t)s.x, 1);
+                } else {
+                    if (fig_polish_insert(out->edit + s0, n0, &out->edit_end[g], s.x, acc[a].second) != 1) { out->state[g] |= FIG_POLISH_CAPPED; continue; }
+                    str.insert((size_t)s.x, 1, "ACGT"[acc[a].second]);
+                }
+                for (int64_t r = 0; r < cnt; r++) if (wpos[(size_t)(base + r)] != INT32_MIN) wpos[(size_t)(base + r)] = fig_polish_shift(wpos[(size_t)(base + r)], s.kind, s.x);
+                applied++;
+            }
+            if (!applied) { saved.pop_back(); active[(size_t)g] = 0; }                                 // every accepted edit was dropped
+        }
+        if (saved.empty()) break;
+        // verify: the next pass over the edited strings
+        compact();
+        for (int64_t g = 0; g < ng; g++) if (out->state[g] & FIG_POLISH_ON) { wlen[(size_t)g] = (int32_t)cur[(size_t)g].size(); wdl[2 * (size_t)g] = wlen[(size_t)g]; }
+        fig_gap_results wf;
+        memset(&wf, 0, sizeof(wf));
+        wf.filled_len = wlen.data(); wf.str_off = wso.data(); wf.str = &wstr[0]; wf.str_capacity = (int64_t)wstr.size();
+        wf.draw_pos = wpos.data(); wf.draw_isz = f->draw_isz; wf.draw_len = wdl.data();
+        Pass V;
+        V.size(um, (size_t)wso[(size_t)ng], gm);
+        FIG_TRY(fig_indel_pass(ctx, &wf, origin, &V.gi, info));
+        ms_indel += info.ms;
+        for (int64_t g = 0; g < ng; g++) if ((out->state[g] & FIG_POLISH_ON) && V.st[(size_t)g] != FIG_INDEL_ON) return FIG_EHIP;      // (cannot happen: n >= 1 and the header follows n)
+        for (const Saved &S : saved) {
+            const int64_t g = S.g, base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU, s0 = f->str_off[g];
+            const int32_t n_old = (int32_t)S.str.size(), n_new = (int32_t)cur[(size_t)g].size();
+            double Vn = 0.0, Vo = 0.0;
+            for (int64_t r = 0; r < cnt; r++) {
+                if (!fig_indel_aligned(S.pos[(size_t)r], hlen[(size_t)(base + r)], n_old) || !fig_indel_aligned(wpos[(size_t)(base + r)], hlen[(size_t)(base + r)], n_new)) continue;
+                Vn = Vn + V.ll[(size_t)(base + r)]; Vo = Vo + curll[(size_t)(base + r)];
+            }
+            if (fig_polish_keep(Vn, Vo)) {
+                out->state[g] |= FIG_POLISH_EDITED;
+                for (int64_t r = 0; r < cnt; r++) curll[(size_t)(base + r)] = V.ll[(size_t)(base + r)];
+                calls[(size_t)g].assign(V.call, (size_t)wso[(size_t)g], (size_t)n_new);
+                call_end[(size_t)g] = V.call_end[(size_t)g];
+            } else {
+                out->state[g] |= FIG_POLISH_REVERTED; n_rev++;
+                cur[(size_t)g] = S.str;
+                std::copy(S.pos.begin(), S.pos.end(), wpos.begin() + base);
+                std::copy(S.edit.begin(), S.edit.end(), out->edit + s0);
+                out->edit_end[g] = S.edit_end;
+                wlen[(size_t)g] = n_old; wdl[2 * (size_t)g] = n_old;
+                active[(size_t)g] = 0;
+            }
+        }
+    }
+    for (int64_t g = 0; g < ng; g++) {
+        if (!(out->state[g] & FIG_POLISH_ON)) continue;
+        if (active[(size_t)g] && (calls[(size_t)g].find_first_not_of('.') != std::string::npos || call_end[(size_t)g] != '.')) out->state[g] |= FIG_POLISH_CAPPED;
+        const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU, s0 = f->str_off[g];
+        const int32_t n0 = f->filled_len[g], n1 = (int32_t)cur[(size_t)g].size();
+        out->polished_len[g] = n1;
+        out->n_ins[g] = fig_polish_k(out->edit_end[g]);
+        for (int32_t x = 0; x < n0; x++) { out->n_ins[g] += fig_polish_k(out->edit[s0 + x]); out->n_del[g] += out->edit[s0 + x] & 1; }
+        double lb = 0.0, la = 0.0;
+        for (int64_t r = 0; r < cnt; r++) {
+            if (!fig_indel_aligned(f->draw_pos[base + r], hlen[(size_t)(base + r)], n0) || !fig_indel_aligned(wpos[(size_t)(base + r)], hlen[(size_t)(base + r)], n1)) continue;
+            lb = lb + ll0[(size_t)(base + r)]; la = la + curll[(size_t)(base + r)];
+        }
+        out->ll_before[g] = lb; out->ll_after[g] = la;
+    }
+    for (int64_t r = 0; r < nu; r++) out->draw_pos[r] = wpos[(size_t)r];
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figpolish] gaps on %lld of %lld, rounds %d, sites %lld, candidates scored %lld, edits accepted %lld, rejected %lld, rounds reverted %lld, indel kernels %.3f ms, polish kernels %.3f ms\n",
+                (long long)gaps_on, (long long)ng, rounds_run, (long long)n_sites, (long long)n_cands, (long long)n_acc, (long long)n_rej, (long long)n_rev, ms_indel, ms_polish);
+    return FIG_OK;
+}
+
+extern "C" int fig_polish_apply(const fig_gap_results *filled, const fig_gap_polish *p, int64_t g, char *dst) { return fig_polish_apply_body(filled, p, g, dst); }
 
 extern "C" int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) { return fig_fill_gaps_once(ctx, batch, out); }
 

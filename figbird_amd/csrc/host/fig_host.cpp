@@ -6,6 +6,7 @@
 #include "../fig_placement_host.h"
 #include "../fig_softqual_host.h"
 #include "../fig_indel_host.h"
+#include "../fig_polish_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -791,6 +792,14 @@ bool write_indel(const RunArgs &a, const Batch &b, const Results &r, std::string
     });
 }
 
+bool write_polished(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+    return write_per_gap(a, b, "gappolished.txt", err, [&](FILE *f, size_t g) {
+        fprintf(f, "%d\t%d\t%d\t%d\t%d\t", r.filled_len[g], r.polish_len[g], (int)r.polish_state[g], r.polish_nins[g], r.polish_ndel[g]);
+        if (r.polish_len[g] > 0) fwrite(r.polish_str[g].data(), 1, r.polish_str[g].size(), f);
+        fputc('\n', f);
+    });
+}
+
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     FILE *f = fopen((a.tmp + "draw.txt").c_str(), "w");
     if (!f) { err = "can't write draw.txt"; return false; }
@@ -1228,4 +1237,43 @@ extern "C" int fighost_run_write_indel(void *h, const int32_t *filled_len, const
     R.indel_state.assign(state, state + ng);
     std::string e;
     return written(fighost::write_indel(r->a, r->B, R, e), e, err, errcap);
+}
+
+// ------------------------------------------------------------------ polish (fig_polish_host.h)
+extern "C" int fig_polish_apply(const fig_gap_results *filled, const fig_gap_polish *p, int64_t g, char *dst) { return fig_polish_apply_body(filled, p, g, dst); }
+
+// the rules of the loop, one binding each
+extern "C" int fighost_polish_shift(int32_t o, int kind, int32_t x) { return fig_polish_shift(o, kind, x); }
+extern "C" int fighost_polish_touched(int32_t o, int32_t len, int32_t x) { return fig_polish_touched(o, len, x) ? 1 : 0; }
+extern "C" int fighost_polish_counted(int32_t o, int32_t len, int32_t n, int kind, int32_t x) { return fig_polish_counted(o, len, n, kind, x) ? 1 : 0; }
+// the sites of a round from call [n] and call_end: x and kind [FIG_POLISH_MAX_SITES]; returns how many
+extern "C" int fighost_polish_sites(const char *call, int32_t n, char call_end, int32_t *x, int32_t *kind) { return fig_polish_sites(call, n, call_end, x, kind); }
+extern "C" int fighost_polish_best(const double *T, int m) { return fig_polish_best(T, m); }
+extern "C" int fighost_polish_accept(double Tc, double T0) { return fig_polish_accept(Tc, T0) ? 1 : 0; }
+extern "C" int fighost_polish_keep(double Vnew, double Vold) { return fig_polish_keep(Vnew, Vold) ? 1 : 0; }
+// the edit planes of one gap of n0 original columns: insert base b before / remove current cell y (fig_polish_insert, fig_polish_remove)
+extern "C" int fighost_polish_insert(int32_t *edit, int32_t n0, int32_t *edit_end, int64_t y, int b) { return fig_polish_insert(edit, n0, edit_end, y, b); }
+extern "C" int fighost_polish_remove(int32_t *edit, int32_t n0, int32_t *edit_end, int64_t y) { return fig_polish_remove(edit, n0, edit_end, y); }
+
+// gappolished.txt of the WHOLE gap set (FIGFILL_POLISH=1): the strings and edit planes indexed like the strings, the rest [n_gaps]; the
+// polished strings are rebuilt here by fig_polish_apply
+extern "C" int fighost_run_write_polished(void *h, const int32_t *filled_len, const int64_t *str_off, const char *str, const int32_t *edit, const int32_t *edit_end,
+                                          const int32_t *polished_len, const uint8_t *state, const int32_t *n_ins, const int32_t *n_del, char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size();
+    fighost::Results R = side_results(r, filled_len, str_off);
+    fig_gap_results f; memset(&f, 0, sizeof(f));
+    f.filled_len = const_cast<int32_t *>(filled_len); f.str_off = const_cast<int64_t *>(str_off); f.str = const_cast<char *>(str);
+    fig_gap_polish p; memset(&p, 0, sizeof(p));
+    p.edit = const_cast<int32_t *>(edit); p.edit_end = const_cast<int32_t *>(edit_end); p.polished_len = const_cast<int32_t *>(polished_len); p.state = const_cast<uint8_t *>(state);
+    R.polish_str.assign(ng, std::string());
+    R.polish_len.assign(polished_len, polished_len + ng); R.polish_nins.assign(n_ins, n_ins + ng); R.polish_ndel.assign(n_del, n_del + ng);
+    R.polish_state.assign(state, state + ng);
+    std::string e;
+    for (size_t g = 0; g < ng; g++) {
+        if (polished_len[g] <= 0) continue;
+        R.polish_str[g].assign((size_t)polished_len[g], 'N');
+        if (fig_polish_apply(&f, &p, (int64_t)g, &R.polish_str[g][0]) != polished_len[g]) { e = "gappolished.txt: the edit planes of gap " + std::to_string(g) + " do not give its polished length"; return written(false, e, err, errcap); }
+    }
+    return written(fighost::write_polished(r->a, r->B, R, e), e, err, errcap);
 }

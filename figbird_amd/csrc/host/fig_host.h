@@ -97,6 +97,10 @@ struct Results {
     // indel evidence (fig_gap_indel), when asked for: call [str.size()] indexed like str, call_end and FIG_INDEL_* [n_gaps]
     std::string indel_call, indel_call_end;
     std::vector<uint8_t> indel_state;
+    // polish (fig_gap_polish), when asked for: the polished string of every gap, and polished_len, n_ins, n_del and the state bits [n_gaps]
+    std::vector<std::string> polish_str;
+    std::vector<int32_t> polish_len, polish_nins, polish_ndel;
+    std::vector<uint8_t> polish_state;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
@@ -117,6 +121,9 @@ bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::st
 // gapindel.txt (no counterpart in the reference): per gap `g contig start G0 n state C E`, tab-separated, the first five fields as in
 // gapout.txt, state = FIG_INDEL_*, C = the n characters of fig_gap_indel::call ('D', 'I' or '.'; empty for n <= 0), E = call_end
 bool write_indel(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gappolished.txt (no counterpart in the reference): per gap `g contig start G0 n polished_len state n_ins n_del P`, tab-separated,
+// the first five fields as in gapout.txt, state = the FIG_POLISH_* bits, P = the polished string (empty for polished_len <= 0)
+bool write_polished(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // filledContigs.fa + Ncount.txt (FillGaps.cpp:708-926)
 bool write_scaffold(const RunArgs &a, const Scaffold &sc, const Batch &b, const Results &r, std::string &err);
 

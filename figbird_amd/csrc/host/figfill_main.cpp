@@ -19,13 +19,14 @@
 
 using namespace fighost;
 
-// Five calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
+// Six calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
 // written against): bound weakly, and asking for what they compute without them is an error before anything is filled or written.
 extern "C" int fig_fill_resident_ex(fig_ctx *, fig_gap_results *, const fig_gap_support *) __attribute__((weak));
 extern "C" int fig_batch_quality(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_quality *) __attribute__((weak));
 extern "C" int fig_batch_placement(fig_ctx *, const fig_gap_results *, const int32_t *, fig_read_placement *) __attribute__((weak));
 extern "C" int fig_batch_softqual(fig_ctx *, const fig_gap_results *, const int32_t *, fig_read_placement *, fig_gap_softqual *) __attribute__((weak));
 extern "C" int fig_batch_indel(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_indel *) __attribute__((weak));
+extern "C" int fig_batch_polish(fig_ctx *, const fig_gap_results *, const int32_t *, int, fig_gap_polish *) __attribute__((weak));
 
 // The optional outputs: read from the environment once, in main(), and passed down.
 //   FIGFILL_SUPPORT=1    also the per-base read support and <tmp>/gapsupport.txt
@@ -33,19 +34,23 @@ extern "C" int fig_batch_indel(fig_ctx *, const fig_gap_results *, const int32_t
 //   FIGFILL_PLACEMENT=1  the fill with the support call, then fig_batch_placement, and <tmp>/gapplacement.txt
 //   FIGFILL_SOFTQUALITY=1  the fill with the support call, then fig_batch_softqual, and <tmp>/gapsoftquality.txt
 //   FIGFILL_INDEL=1      the fill with the support call, then fig_batch_indel, and <tmp>/gapindel.txt
+//   FIGFILL_POLISH=1     the fill with the support call, then fig_batch_polish (FIGFILL_POLISH_ROUNDS=<k>: its max_rounds), and
+//                        <tmp>/gappolished.txt; filledContigs.fa keeps the unpolished strings
 //   FIGFILL_QUALITY_MINPQ=<k> (only together with FIGFILL_QUALITY=1): the quality leaves out scored reads with pq < k
 struct Wants {
-    bool support_file = false, quality = false, placement_file = false, softquality = false, indel = false;
+    bool support_file = false, quality = false, placement_file = false, softquality = false, indel = false, polish = false;
     int min_pq = -1;                                                            // -1 = not set
+    int polish_rounds = 0;                                                      // 0 = the library's default
     bool placement() const { return placement_file || min_pq >= 0; }            // the call is needed for the file and for the filter
-    bool support() const { return support_file || quality || placement() || softquality || indel; }
+    bool support() const { return support_file || quality || placement() || softquality || indel || polish; }
 };
 
 static Wants wants_from_env() {
     auto is1 = [](const char *name) { const char *s = getenv(name); return s && atoi(s) == 1; };
     Wants w;
     w.support_file = is1("FIGFILL_SUPPORT"); w.quality = is1("FIGFILL_QUALITY"); w.placement_file = is1("FIGFILL_PLACEMENT"); w.softquality = is1("FIGFILL_SOFTQUALITY");
-    w.indel = is1("FIGFILL_INDEL");
+    w.indel = is1("FIGFILL_INDEL"); w.polish = is1("FIGFILL_POLISH");
+    if (const char *k = getenv("FIGFILL_POLISH_ROUNDS")) w.polish_rounds = w.polish ? atoi(k) : 0;
     const char *s = getenv("FIGFILL_QUALITY_MINPQ");
     w.min_pq = s && *s && w.quality ? atoi(s) : -1;
     return w;
@@ -97,6 +102,25 @@ static int indel_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, i
     return fig_batch_indel(ctx, fr, R.sup_origin.data(), &gi);
 }
 
+// the polish of the fill `fr` just returned (the batch still resident): R.polish_str and the four per-gap arrays
+static int polish_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu, int rounds) {
+    const size_t m = (size_t)std::max<int64_t>(nu, 1), t = (size_t)std::max<int64_t>(fr->str_off[ng], 1), gm = (size_t)std::max<int64_t>(ng, 1);
+    R.polish_str.assign(gm, std::string()); R.polish_len.assign(gm, 0); R.polish_nins.assign(gm, 0); R.polish_ndel.assign(gm, 0); R.polish_state.assign(gm, 0);
+    std::vector<int32_t> i(t + m + 2 * gm, 0);
+    std::vector<double> d(2 * gm, 0.0);
+    fig_gap_polish gp;
+    gp.edit = i.data(); gp.draw_pos = i.data() + t; gp.edit_end = gp.draw_pos + m; gp.rounds = gp.edit_end + gm;
+    gp.polished_len = R.polish_len.data(); gp.n_ins = R.polish_nins.data(); gp.n_del = R.polish_ndel.data();
+    gp.ll_before = d.data(); gp.ll_after = d.data() + gm; gp.state = R.polish_state.data();
+    const int rc = fig_batch_polish(ctx, fr, R.sup_origin.data(), rounds, &gp);
+    for (int64_t g = 0; !rc && g < ng; g++) {
+        if (R.polish_len[(size_t)g] <= 0) continue;
+        R.polish_str[(size_t)g].assign((size_t)R.polish_len[(size_t)g], 'N');
+        if (fig_polish_apply(fr, &gp, g, &R.polish_str[(size_t)g][0]) != R.polish_len[(size_t)g]) return FIG_EINVAL;
+    }
+    return rc;
+}
+
 // The fill of the batch `fb` (nu unmapped + np partial reads) resident in ctx, as both the single-device path and a shard run it:
 // R is sized, `fr` -- zeroed by the caller, who may have set its dbg_* fields -- becomes the view of R the library fills, then
 // the fill (with R.sup_counts / R.sup_origin when `w` needs the support call) and the passes beside it that `w` asks for.
@@ -124,6 +148,7 @@ static int fill_batch(fig_ctx *ctx, const fig_model *fm, const fig_gap_batch *fb
     if (!rc && w.quality) { what = "fig_batch_quality"; rc = quality_resident(ctx, &fr, R, ng, nu, w.min_pq); }
     if (!rc && w.softquality) { what = "fig_batch_softqual"; rc = softquality_resident(ctx, &fr, R, ng); }
     if (!rc && w.indel) { what = "fig_batch_indel"; rc = indel_resident(ctx, &fr, R, ng, nu); }
+    if (!rc && w.polish) { what = "fig_batch_polish"; rc = polish_resident(ctx, &fr, R, ng, nu, w.polish_rounds); }
     return rc;
 }
 
@@ -131,7 +156,8 @@ static int fill_batch(fig_ctx *ctx, const fig_model *fm, const fig_gap_batch *fb
 static bool write_outputs(const RunArgs &a, const Scaffold &sc, const Batch &B, const Results &R, const Wants &w, std::string &err) {
     return write_gapout(a, B, R, err) && write_draw(a, B, R, err) && write_gaploads(a, B, err) && write_scaffold(a, sc, B, R, err) &&
            (!w.support_file || write_support(a, B, R, err)) && (!w.quality || write_quality(a, B, R, err)) && (!w.placement_file || write_placement(a, B, R, err)) &&
-           (!w.softquality || write_softquality(a, B, R, err)) && (!w.indel || write_indel(a, B, R, err));
+           (!w.softquality || write_softquality(a, B, R, err)) && (!w.indel || write_indel(a, B, R, err)) &&
+           (!w.polish || write_polished(a, B, R, err));
 }
 
 static int fail(const std::string &m) { fprintf(stderr, "%s\n", m.c_str()); return 1; }
@@ -220,6 +246,10 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
     if (quality) R.qual_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
     if (w.softquality) R.softq_state.assign((size_t)std::max<int64_t>(ng, 1), 0);
     if (w.indel) { R.indel_call_end.assign((size_t)std::max<int64_t>(ng, 1), '.'); R.indel_state.assign((size_t)std::max<int64_t>(ng, 1), 0); }
+    if (w.polish) {
+        const size_t gm = (size_t)std::max<int64_t>(ng, 1);
+        R.polish_str.assign(gm, std::string()); R.polish_len.assign(gm, 0); R.polish_nins.assign(gm, 0); R.polish_ndel.assign(gm, 0); R.polish_state.assign(gm, 0);
+    }
     for (int64_t g = 0; g < ng; g++) {
         const ShardRun &S = runs[owner[g]]; const int64_t k = local[g];
         R.filled_len[g] = S.R.filled_len[k]; R.gaptofill[g] = S.R.gaptofill[k];
@@ -240,6 +270,10 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         if (w.indel) {
             R.indel_call.append(S.R.indel_call, (size_t)S.R.str_off[k], (size_t)(S.R.str_off[k + 1] - S.R.str_off[k]));
             R.indel_call_end[g] = S.R.indel_call_end[k]; R.indel_state[g] = S.R.indel_state[k];
+        }
+        if (w.polish) {                                   // the polished strings are per gap already
+            R.polish_str[g] = S.R.polish_str[k]; R.polish_len[g] = S.R.polish_len[k]; R.polish_nins[g] = S.R.polish_nins[k]; R.polish_ndel[g] = S.R.polish_ndel[k];
+            R.polish_state[g] = S.R.polish_state[k];
         }
         R.draw_len[2 * g] = S.R.draw_len[2 * k]; R.draw_len[2 * g + 1] = S.R.draw_len[2 * k + 1];
         const int64_t nu = B.u_read_off[g + 1] - B.u_read_off[g], np = B.p_read_off[g + 1] - B.p_read_off[g];
@@ -291,6 +325,7 @@ int main(int argc, char **argv) {
         return fail("figfill: FIGFILL_PLACEMENT=1 and FIGFILL_QUALITY_MINPQ need fig_batch_placement, which the library behind this build does not export");
     if (w.softquality && !fig_batch_softqual) return fail("figfill: FIGFILL_SOFTQUALITY=1 needs fig_batch_softqual, which the library behind this build does not export");
     if (w.indel && !fig_batch_indel) return fail("figfill: FIGFILL_INDEL=1 needs fig_batch_indel, which the library behind this build does not export");
+    if (w.polish && !fig_batch_polish) return fail("figfill: FIGFILL_POLISH=1 needs fig_batch_polish, which the library behind this build does not export");
     if (w.quality && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
     setenv("GPU_MAX_HW_QUEUES", "8", 0);                 // one hardware queue per scheduler lane; before any thread or HIP call (fig_abi.hip: fig_ctx_create)
     auto t0 = std::chrono::steady_clock::now();

@@ -47,6 +47,12 @@ PLANES = (
     ("indel", "icl", lambda r: r.indel.call, "byte", (), np.uint8, ord(".")),
     ("indel", "ice", lambda r: r.indel.call_end, "gap", (), np.uint8, ord(".")),
     ("indel", "ist", lambda r: r.indel.state, "gap", (), np.uint8, 0),
+    ("polish", "oed", lambda r: r.polish.edit, "byte", (), np.int32, 0),
+    ("polish", "oee", lambda r: r.polish.edit_end, "gap", (), np.int32, 0),
+    ("polish", "oln", lambda r: r.polish.polished_len, "gap", (), np.int32, 0),
+    ("polish", "ost", lambda r: r.polish.state, "gap", (), np.uint8, 0),
+    ("polish", "oni", lambda r: r.polish.n_ins, "gap", (), np.int32, 0),
+    ("polish", "ond", lambda r: r.polish.n_del, "gap", (), np.int32, 0),
 )
 
 
@@ -63,9 +69,11 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     # read (fig_read_placement) -- any of them runs the fill with the support call; FIGFILL_QUALITY_MINPQ=<k> (only with
     # FIGFILL_QUALITY=1): the quality leaves out the scored reads with pq < k; FIGFILL_SOFTQUALITY=1: also gapsoftquality.txt, the
     # per-base Phred summed over read placements (fig_gap_softqual); FIGFILL_INDEL=1: also gapindel.txt, the indel call per filled base
-    # (fig_gap_indel)
-    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality", "indel")}
-    support, quality, placement, softquality, indel = on["support"], on["quality"], on["placement"], on["softquality"], on["indel"]
+    # (fig_gap_indel); FIGFILL_POLISH=1 (FIGFILL_POLISH_ROUNDS=<k>: max_rounds): also gappolished.txt, the polished strings
+    # (fig_gap_polish): the edit planes travel, and rank 0 rebuilds the strings with the host library's fig_polish_apply
+    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality", "indel", "polish")}
+    support, quality, placement, softquality, indel, polish = on["support"], on["quality"], on["placement"], on["softquality"], on["indel"], on["polish"]
+    polish_rounds = (_env_int("FIGFILL_POLISH_ROUNDS") or 0) if polish else 0
     min_pq = _env_int("FIGFILL_QUALITY_MINPQ") if quality else None
     if min_pq is not None and min_pq < 0:
         min_pq = None
@@ -132,8 +140,8 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
             preset = np.zeros(max(n, 1), dtype=np.uint8)
             host.fighost_run_ot_presets(h, api._p(reach, api.c_u8_p), api._p(preset, api.c_u8_p))
             eng.set_ot_preset(preset[mine] if len(mine) else np.zeros(0, dtype=np.uint8))
-            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality or indel, quality=quality, placement=placement, min_pq=min_pq,
-                                  softqual=softquality, indel=indel)
+            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality or indel or polish, quality=quality, placement=placement, min_pq=min_pq,
+                                  softqual=softquality, indel=indel, polish=polish, polish_rounds=polish_rounds)
             st = eng.stats()
             eng.close()
         except Exception as e:
@@ -201,6 +209,10 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 if wrc == 0 and indel:
                     wrc = host.fighost_run_write_indel(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p),
                                                        C.cast(G["icl"].ctypes.data, C.c_char_p), C.cast(G["ice"].ctypes.data, C.c_char_p), api._p(G["ist"], api.c_u8_p), err, 512)
+                if wrc == 0 and polish:
+                    wrc = host.fighost_run_write_polished(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p), C.cast(raw.ctypes.data, C.c_char_p),
+                                                          api._p(G["oed"], api.c_i32_p), api._p(G["oee"], api.c_i32_p), api._p(G["oln"], api.c_i32_p), api._p(G["ost"], api.c_u8_p),
+                                                          api._p(G["oni"], api.c_i32_p), api._p(G["ond"], api.c_i32_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

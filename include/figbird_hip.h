@@ -349,6 +349,86 @@ typedef struct fig_gap_indel {
     uint8_t *state;      /* [n_gaps] FIG_INDEL_* */
 } fig_gap_indel;
 
+/* Optional polish of the filled strings (fig_batch_polish): the indel calls of fig_gap_indel that the reads' likelihood confirms are
+ * applied, round by round, and the result is verified.  fig_gap_indel says that most reads want a base before column 45; it does not
+ * say which base, nor whether the edit raises the reads' likelihood, and it leaves the string as it is.  Every term not redefined
+ * here means what it means for fig_gap_indel: S(x), n, the tables, the band with W = 7, ll_gapped, the calls, which gaps are on and
+ * which reads are scored and aligned.
+ *
+ * Candidate edits of a gap whose current string has n columns.  DEL x removes column x (0 <= x < n, n >= 2).  INS x b puts base b,
+ * one of ACGT, before column x (0 <= x <= n).  The edited sequence S_c(y) over all integer columns y:
+ *   DEL x:    S(y) for y < x, S(y+1) for y >= x;
+ *   INS x b:  S(y) for y < x, b for y = x, S(y-1) for y > x;
+ * its length is n_c = n -+ 1.  A read's offset under the candidate, o_c: o* + 1 for INS when o* >= x; o* - 1 for DEL when o* > x;
+ * otherwise o*.
+ *
+ * Reads.  A read is TOUCHED iff o* - (W+1) <= x <= o* + len + W: a read that is not touched has the same band contents under S_c
+ * and o_c.  A read is COUNTED iff it is scored, touched, aligned under (o*, n) and aligned under (o_c, n_c).
+ *
+ * Scores.  ll_c(r) is fig_gap_indel's ll_gapped of read r against S_c at o_c: the same cell update, sweep and end order, no
+ * traceback; it is reproducible bit for bit.  T_c is the sum of ll_c(r) over the counted reads and T_0 the sum of the unedited
+ * ll_gapped(r) over the same reads, both in ascending read index from 0.0, one IEEE addition each.  Only -inf can occur: no NaN.
+ *
+ * One round, per gap that is on and has not stopped:
+ *   1 sites       the columns with call != '.', ascending, then the right junction if call_end != '.'; the first
+ *                 FIG_POLISH_MAX_SITES = 16 of them, the rest wait for the next round.  A gap without a site stops.
+ *   2 candidates  a 'D' site proposes DEL x; an 'I' site INS x A, INS x C, INS x G, INS x T; call_end the four at x = n.  A site
+ *                 is skipped, and the gap gets FIG_POLISH_CAPPED, where the edit cannot be stored: DEL at n = 1, or INS into a list
+ *                 of inserted bases that already holds 7 (see edit below).
+ *   3 best        per site the candidate of the greatest T_c; ties go to the first of A, C, G, T.
+ *   4 accept      the best is accepted iff T_c > T_0; otherwise the gap gets FIG_POLISH_REJECTED.  A gap with no accepted
+ *                 candidate stops.
+ *   5 apply       the accepted edits of the gap are applied together, right to left, each shifting the offsets of all the gap's
+ *                 drawn reads by the rule of o_c.  An edit that can no longer be stored when its turn comes (the two cases of step
+ *                 2, after the edits to its right) is dropped and the gap gets FIG_POLISH_CAPPED.
+ *   6 verify      the next indel pass runs over the edited strings and offsets.  V_new is the sum of the new ll_gapped and V_old
+ *                 the sum of the old, over the gap's reads aligned under both the old and the new (offset, n), in ascending read
+ *                 index from 0.0.  The round is kept iff V_new > V_old (FIG_POLISH_EDITED); otherwise the gap takes its previous
+ *                 string and offsets back, gets FIG_POLISH_REVERTED and stops.
+ *   7 stop        the calls of the verifying pass are the sites of the next round.  A gap that has not stopped after max_rounds
+ *                 rounds and still has a call gets FIG_POLISH_CAPPED.
+ * rounds[g] counts the rounds in which the gap had a site.
+ *
+ * Result, in terms of the ORIGINAL columns 0 <= x < n of the caller's string, compacted like str:
+ *   edit[x]      bit 0: the column's base is removed; bits 1-3: k, the number of bases inserted immediately before it (0..7);
+ *                bits 4+2i, 5+2i: the code (A C G T = 0..3) of inserted base i, leftmost first
+ *   edit_end[g]  the same layout for the bases after the last column; bit 0 is never set
+ * The polished string is, over x: the inserted bases of edit[x], then str[x] unless removed; then the bases of edit_end[g]
+ * (fig_polish_apply).  An insertion before a current cell that is an original column joins the end of that column's list (of
+ * edit_end's list for x = n); before a cell that is itself an inserted base it takes that position in the same list.  Removing an
+ * inserted base takes it out of its list.
+ *   polished_len  [n_gaps] the length of the polished string
+ *   draw_pos      [n_ureads] the offsets against the polished strings; INT32_MIN is kept
+ *   n_ins, n_del  [n_gaps] inserted bases and removed columns in force at the end
+ *   ll_before, ll_after  [n_gaps] the sum of ll_gapped against the original and against the polished string, over the gap's reads
+ *                 aligned under both, in ascending read index from 0.0: equal bit for bit for an unedited gap
+ *   state         FIG_POLISH_ON | EDITED | REJECTED | REVERTED | CAPPED
+ * Off gaps get zeros, their own filled_len and the caller's draw_pos, written by the library whatever the buffers held.
+ *
+ * Limits: everything fig_gap_indel lists; edits are judged one site at a time against the unedited string of the round and only
+ * verified jointly; the read set and the drawn offsets are those of the fill -- nothing is placed again; at most one base per site
+ * and round. */
+#define FIG_POLISH_ON        1
+#define FIG_POLISH_EDITED    2
+#define FIG_POLISH_REJECTED  4
+#define FIG_POLISH_REVERTED  8
+#define FIG_POLISH_CAPPED    16
+#define FIG_POLISH_MAX_SITES 16
+#define FIG_POLISH_MAX_ROUNDS 8
+#define FIG_POLISH_DEFAULT_ROUNDS 4
+typedef struct fig_gap_polish {
+    int32_t *edit;          /* [str_off[n_gaps]] */
+    int32_t *edit_end;      /* [n_gaps] */
+    int32_t *polished_len;  /* [n_gaps] */
+    int32_t *draw_pos;      /* [n_ureads] */
+    int32_t *n_ins;         /* [n_gaps] */
+    int32_t *n_del;         /* [n_gaps] */
+    int32_t *rounds;        /* [n_gaps] */
+    double  *ll_before;     /* [n_gaps] */
+    double  *ll_after;      /* [n_gaps] */
+    uint8_t *state;         /* [n_gaps] FIG_POLISH_* bits */
+} fig_gap_polish;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -423,6 +503,18 @@ int fig_batch_softqual(fig_ctx *ctx, const fig_gap_results *filled, const int32_
  * batch and the model and writes neither.  With FIG_SCHED_LOG set, one "[figindel]" line on stderr: gaps on, reads aligned, reads
  * with an event, columns called, HIP-event milliseconds of the kernel. */
 int fig_batch_indel(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, fig_gap_indel *out);
+
+/* Polish of the strings in `filled` against the RESIDENT batch (see fig_gap_polish); `filled` and origin as for fig_batch_indel.
+ * max_rounds: 1..8, or 0 for the default of 4.  FIG_EINVAL under fig_batch_indel's conditions (they hold for the shifted offsets
+ * too), with a NULL member of `out`, or with max_rounds outside 0..8.  Reads the resident batch and the model and writes neither;
+ * the caller's `filled` is never changed.  At most max_rounds + 1 launches of the indel kernel and max_rounds of the polish kernel.
+ * With FIG_SCHED_LOG set, one "[figpolish]" line on stderr: gaps on, rounds, sites, candidates scored, edits accepted, rejected and
+ * reverted, HIP-event milliseconds of the indel launches and of the polish launches. */
+int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, int max_rounds, fig_gap_polish *out);
+
+/* The polished string of gap g from the caller's strings and the edit planes of `p`: writes polished_len[g] bytes to dst (nothing when
+ * dst is NULL) and returns that length, or a negative FIG_E* code.  Needs no context and no device. */
+int fig_polish_apply(const fig_gap_results *filled, const fig_gap_polish *p, int64_t g, char *dst);
 
 int fig_get_stats(const fig_ctx *ctx, fig_stats *out);
 
