@@ -488,6 +488,7 @@ static hipError_t launch_kind(fig_ctx *ctx, const fig_ctx::Cls &c, const FigDevB
     FigKernArgs A = fig_kargs_of(c.c, qsel, ctx->sh_on);
     if (kind == FIG_K_EVAL) { const FigKnobs &kn = ctx->fill_knobs; A.cont = kn.cont && db.cont_cap > 0; A.minc = kn.minc; A.cont_live = kn.cont_live; A.cont_prio = kn.cont_prio;
                               A.wide = A.cont ? wide : 0; A.wide_base = ctx->nslots; A.wide_cap = ctx->nslots_wide; }
+    if (kind != FIG_K_PROBE) A.mle_reuse = ctx->fill_knobs.mle_reuse;      // the kernels of a fill (the reach pre-pass is partial mode's: off there)
     switch (kind) {
         case FIG_K_FILL: return launch_one(fig_fill_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
         case FIG_K_BEGIN: return launch_one(fig_begin_kernel<LDS_TAB, NT>, c.c.lds, NT, blocks, stream, ctx->dm, db, A);
@@ -828,6 +829,7 @@ extern "C" int fig_fill_resident_ex(fig_ctx *ctx, fig_gap_results *out, const fi
 #endif
     if (knobs.log) fprintf(stderr, "[figsched] useful flops %.4g, speculative evaluations executed %.4g (%.1f %% discarded)\n", (double)cnt[FIG_CNT_FLOPS], (double)cnt[FIG_CNT_SPEC], cnt[FIG_CNT_SPEC] ? 100.0 * (1.0 - ((double)cnt[FIG_CNT_FLOPS] / (double)cnt[FIG_CNT_SPEC])) : 0.0);
     if (knobs.log && knobs.wide) fprintf(stderr, "[figsched] widened chunks narrowed to the live workgroups: %llu\n", cnt[FIG_CNT_NARROW]);
+    if (knobs.log && knobs.mle_reuse) fprintf(stderr, "[figsched] MLE passes reused: %llu of %llu placeReads calls executed (%.1f %%)\n", cnt[FIG_CNT_MLE_REUSED], cnt[FIG_CNT_MLE_ASKED], cnt[FIG_CNT_MLE_ASKED] ? 100.0 * (double)cnt[FIG_CNT_MLE_REUSED] / (double)cnt[FIG_CNT_MLE_ASKED] : 0.0);
     fig_stats_from_counters(cnt, ctx->stats);
     int rc = fig_compact_results(ng, hstr.data(), ctx->h_str_off.data(), out);
     if (!rc && sup) fig_compact_support(ng, hsup.data(), ctx->h_str_off.data(), out, sup->counts);

@@ -226,6 +226,9 @@ struct FigKnobs {
     // FIG_ESTEP=pair: the pair-chain E-step everywhere (A/B runs, tests); FIG_SH_CHUNKS=<1..4>: chunks per super-chunk of the
     // shared-factor E-step (fig_engine_shared.h; default 4: bench step 24.3 s with 2, 23.9 s with 4)
     int sh_on;
+    // FIG_MLE_REUSE=0: every unmapped placeReads call runs its MLE pass; default (on, unmapped mode only): a call whose E-step
+    // consensus equals that of the candidate's previous call takes the previous pass's outputs (fig_engine_core.h: fig_mle_reuse_*)
+    int mle_reuse;
 };
 
 #define FIG_WIDE_DEFAULT_UNMAPPED FIG_WIDE_GROW
@@ -251,6 +254,8 @@ static FigKnobs fig_knobs_from_env(int unmapped) {
     k.minc = mc ? std::max(1, atoi(mc)) : 16;
     k.ipw = ipw ? std::max(1.0, atof(ipw)) : (unmapped ? 12.0 : 6.0);
     k.sh_on = (ev && !strcmp(ev, "pair")) ? 0 : (sc ? std::max(1, std::min(FIG_SH_SC, atoi(sc))) : FIG_SH_SC);
+    const char *mr = getenv("FIG_MLE_REUSE");
+    k.mle_reuse = unmapped != 0 && !(mr && !strcmp(mr, "0"));
     return k;
 }
 

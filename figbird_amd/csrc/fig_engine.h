@@ -72,6 +72,9 @@ FIG_D unsigned long long fig_shfl_down_u64(unsigned long long v, int off) { retu
 #define FIG_NOPOS 0x7fffffff
 #define FIG_PLB_TEAMS 8
 #define FIG_PLB_BYTES (FIG_PLB_TEAMS * 64 * 4)
+// Slots of FigScr::mr_key: what mode 0 of the MLE pass depends on besides the consensus string (constant within a candidate
+// evaluation, compared all the same), the valid bit, and the pass's contribution to S.valid_count
+enum FigMrKey { FIG_MR_G = 0, FIG_MR_LEFT, FIG_MR_RIGHT, FIG_MR_NCOLS, FIG_MR_GAPOFF, FIG_MR_VALID, FIG_MR_VCOUNT, FIG_MR_KEYS = 8 };
 
 // Optional phase timers (diagnostic build only: -DFIG_PROF).  Every lane accumulates s_memtime deltas in its own
 // FigEng::prof[] (no atomics inside the loops); lane 0 of each wave adds them to its FIG_CNT_PROF_* counter when the kernel
@@ -212,6 +215,13 @@ struct FigScr {
     int *used_read_arr; int *lrmd;                    // [C], [C][2]
     FigPQ *pqg; double *q4g;   // extended probability table when it does not fit in LDS
     double *wg;        // global weight buffer when it does not fit in LDS
+    // MLE reuse (fig_mle_reuse_*, fig_engine_core.h): the last executed mode-0 pass of the candidate under evaluation
+    unsigned char *mr_gs;   // [capG] the consensus it searched against (E.gs)
+    unsigned char *mr_acc;  // [R] its accf
+    double *mr_maxlv;       // [R] its maxlv of the accepted reads
+    int *mr_frp;            // [R][2] its frp of the accepted reads (org is the same pair when G == G0)
+    int *mr_key;            // [FIG_MR_KEYS] FigMrKey: the scalars it ran under, the valid bit, its valid_count
+    unsigned long long *mr_credit;   // [16] the algorithmic flops it credited, per wave of the workgroup
 };
 
 FIG_HD long long fig_align8(long long x) { return (x + 15) & ~15LL; }   // (16: FigPQ rows want ds_read_b128 / dwordx4 alignment)
@@ -258,6 +268,12 @@ FIG_HD long long fig_scratch_layout(unsigned char *base, int capG, int capR, int
     FIG_CARVE(accf, unsigned char, capR + 8);
     FIG_CARVE(mdone, unsigned char, capR + 8);
     FIG_CARVE(smflag, unsigned char, capP + 8);
+    FIG_CARVE(mr_maxlv, double, capR);
+    FIG_CARVE(mr_credit, unsigned long long, 16);
+    FIG_CARVE(mr_frp, int, 2LL * capR);
+    FIG_CARVE(mr_key, int, FIG_MR_KEYS);
+    FIG_CARVE(mr_gs, unsigned char, capG + 8);
+    FIG_CARVE(mr_acc, unsigned char, capR + 8);
 #undef FIG_CARVE
     return o;
 }
@@ -283,6 +299,7 @@ struct FigEng {
     double *wbuf;                    // [nteams][Wcap]
     int Wcap, nteams;
     int sh_on;                       // the shared-factor E-step may be used (FIG_ESTEP=pair switches it off)
+    int mle_reuse;                   // an unmapped placeReads call may reuse the previous call's MLE pass (FIG_MLE_REUSE=0 switches it off)
     int lane, wave, nw, wsz;         // lane in wave, wave in workgroup, waves per workgroup, lanes per wave
     const double *kt_fwd, *kt_rev;   // {1-e[k], e[k]} pairs, forward and reversed (index (L-len)+j), for scalar loads
     const double *mt_fwd, *mt_rev;   // {1-e-ins-del, e[k]} pairs for the MLE pass
@@ -306,7 +323,8 @@ FIG_D void fig_eng_ident(FigEng &E, unsigned tid, unsigned nt, unsigned wsz) {
 // What a launch hands its workgroups besides model and batch: the class's capacities and memory form, the queue range.
 struct FigKernArgs { int capG, capGl, ncolE, Wcap, nteams, q_begin, q_end, qsel, tiles, tile_step, tile_cols, tiled_max, sh_on;
                      int cont = 0, minc = 16, cont_live = 100, cont_prio = 1;      // continuous form of the eval launch (FigKnobs, fig_abi_host.h)
-                     int wide = 0, wide_base = 64, wide_cap = 64; };               // its wide chunks: FIG_WIDE bits, base slots, wide cap (FigWide, fig_engine_sched.h)
+                     int wide = 0, wide_base = 64, wide_cap = 64;                  // its wide chunks: FIG_WIDE bits, base slots, wide cap (FigWide, fig_engine_sched.h)
+                     int mle_reuse = 0; };                                         // FIG_MLE_REUSE (FigKnobs, fig_abi_host.h)
 
 // LDS / slab carve-up of a workgroup (doubles first so everything stays 8-byte aligned):
 //   LDS table:  PQ[4][ncolE] (16 B each)  Q4[ncolE]  wbuf[nteams][Wcap]  | FigState  gs[capGl]  rb[FIG_MAX_READLEN+8]  plb
@@ -316,7 +334,7 @@ struct FigKernArgs { int capG, capGl, ncolE, Wcap, nteams, q_begin, q_end, qsel,
 // Returns the bytes of LDS the layout occupies.
 FIG_D long long fig_eng_carve(FigEng &E, const FigDevModel &M, const FigKernArgs &A, bool lds_tab) {
     E.capG = A.capG;
-    E.ncolE = A.ncolE; E.xoff = M.L - 1; E.Wcap = A.Wcap; E.nteams = A.nteams; E.sh_on = A.sh_on;
+    E.ncolE = A.ncolE; E.xoff = M.L - 1; E.Wcap = A.Wcap; E.nteams = A.nteams; E.sh_on = A.sh_on; E.mle_reuse = A.mle_reuse;
     long long off = 0;
     E.pq_lds = lds_tab; E.w_lds = lds_tab;
     E.tiles = A.tiles; E.tile_step = A.tile_step; E.tile_cols = A.tile_cols;

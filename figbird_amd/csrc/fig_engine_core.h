@@ -356,7 +356,7 @@ FIG_D int fig_find_contig_match(FigEng &E) {
 FIG_D int fig_initialize(FigEng &E, int gl, int negGapCheck) {
     FigState &S = *E.S;
     int cg = E.capG;
-    if (E.tid == 0) { S.G = gl; fig_ise(E); S.region_perct = 0; }
+    if (E.tid == 0) { S.G = gl; fig_ise(E); S.region_perct = 0; if (E.mle_reuse) E.scr.mr_key[FIG_MR_VALID] = 0; }      // (a new evaluation: no MLE pass to reuse)
     FIG_SYNC();
     int G = S.G;
     for (int x = E.tid; x < cg; x += E.nt) {
@@ -711,6 +711,83 @@ FIG_D void fig_dbg_planes(FigEng &E, int nreads) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Reuse of the MLE pass.  Mode 0 of the pass (fig_hot_mle) is a function of the consensus string E.gs, the flanks, the model and
+// the reads, under the scalars (G, left, right, ncols, gapoffset); the hints only steer its search.  Inside one candidate
+// evaluation nothing but E.gs moves, and once the EM loop has settled E.gs repeats from call to call: such a call takes the
+// outputs of the last executed pass from the slab (FigScr::mr_*) instead of searching again.
+//   key    mr_gs[0..ncols) + the five scalars + a valid bit, which fig_initialize clears: every candidate, fig_run and
+//          fig_run_original start cold, and finalize (mode 1) is never concerned
+//   kept   per read accf, the accepted reads' maxlv and frp (mark is accf, org is frp when G == G0); the pass's share of
+//          S.valid_count; its algorithmic credit
+//   as it lies   hint (the arg-max, which the skipped pass would write again), hval / mdone (pass-local), nci and ncnt (written
+//          by the pass and the conversion behind it alone; fig_initialize zeroes ncnt but also clears the valid bit), the three
+//          G0 <= 30 flags (OR-only within a candidate, and the pass that set them ran in it)
+// Under a non-monotone model (fmm_up > 1, the marker of fig_model_fmm) every pass runs, as the pruning is off there too: the
+// accounting "nothing is pruned" stays true.  A model with both partial_flag and unmapped set zeroes ncnt between two passes
+// (the partial branch of fig_place_reads): no reuse there either.
+FIG_D bool fig_mle_reuse_on(const FigEng &E) { return E.mle_reuse && E.M->fmm_up <= 1.0 && !E.M->partial_flag; }
+
+// Is this call's E.gs (complete, behind a barrier) the string of the last executed pass, under the same scalars?  All lanes;
+// the same answer in every lane.  Leaves this call's string in mr_gs either way.
+FIG_D bool fig_mle_reuse_probe(FigEng &E, int gapoffset) {
+    FigState &S = *E.S;
+    const int *key = E.scr.mr_key;
+    if (E.tid == 0) S.ibuf[0] = key[FIG_MR_VALID] == 1 && key[FIG_MR_G] == S.G && key[FIG_MR_LEFT] == S.left && key[FIG_MR_RIGHT] == S.right &&
+                                key[FIG_MR_NCOLS] == S.ncols && key[FIG_MR_GAPOFF] == gapoffset;
+    FIG_SYNC();
+    int neq = 0;
+    for (int x = E.tid; x < S.ncols; x += E.nt) { const unsigned char c = E.gs[x]; if (E.scr.mr_gs[x] != c) { neq = 1; E.scr.mr_gs[x] = c; } }
+    if (neq) S.ibuf[0] = 0;
+    FIG_SYNC();
+    const int same = S.ibuf[0];
+    FIG_SYNC();
+    if (E.tid == 0) { fig_atomic_add_u64(&E.B->counters[FIG_CNT_MLE_ASKED], 1ull); if (same) fig_atomic_add_u64(&E.B->counters[FIG_CNT_MLE_REUSED], 1ull); }
+    return same != 0;
+}
+
+// After an executed pass (its closing barrier passed, nothing of the call's tail run yet): keep what fig_mle_reuse_restore puts
+// back.  alg: this lane's share of the pass's algorithmic credit; vc0: S.valid_count in front of the pass.
+FIG_D void fig_mle_reuse_keep(FigEng &E, int gapoffset, unsigned long long alg, int vc0) {
+    FigState &S = *E.S;
+    for (int r = E.tid; r < E.g->nU; r += E.nt) {
+        const unsigned char a = E.scr.accf[r];
+        E.scr.mr_acc[r] = a;
+        if (a) { E.scr.mr_maxlv[r] = E.scr.maxlv[r]; E.scr.mr_frp[r * 2] = E.scr.frp[r * 2]; E.scr.mr_frp[r * 2 + 1] = E.scr.frp[r * 2 + 1]; }
+    }
+    for (int off = 32; off > 0; off >>= 1) alg += fig_shfl_down_u64(alg, off);
+    if (E.lane == 0) E.scr.mr_credit[E.wave] = alg;
+    if (E.tid == 0) {
+        int *key = E.scr.mr_key;
+        key[FIG_MR_G] = S.G; key[FIG_MR_LEFT] = S.left; key[FIG_MR_RIGHT] = S.right; key[FIG_MR_NCOLS] = S.ncols; key[FIG_MR_GAPOFF] = gapoffset;
+        key[FIG_MR_VCOUNT] = S.valid_count - vc0; key[FIG_MR_VALID] = 1;
+    }
+}
+
+// A hit: the outputs of the kept pass on top of what fig_place_reads reset on entry, its counts and its credit (no executed
+// multiplies: E.mle_exec stays).  Ends with a barrier, as the pass does.
+FIG_D void fig_mle_reuse_restore(FigEng &E) {
+    FigState &S = *E.S;
+    const bool at_g0 = S.G == E.g->G0;
+    for (int r = E.tid; r < E.g->nU; r += E.nt) {
+        const unsigned char a = E.scr.mr_acc[r];
+        E.scr.accf[r] = a;
+        if (a) {
+            const int of = E.scr.mr_frp[r * 2], len = E.scr.mr_frp[r * 2 + 1];
+            E.scr.maxlv[r] = E.scr.mr_maxlv[r]; E.scr.mark[r] = 1;
+            E.scr.frp[r * 2] = of; E.scr.frp[r * 2 + 1] = len;
+            if (at_g0) { E.scr.org[r * 2] = of; E.scr.org[r * 2 + 1] = len; }
+        }
+    }
+    if (E.tid == 0) {
+        unsigned long long alg = 0;
+        for (int w = 0; w < E.nw; w++) alg += E.scr.mr_credit[w];
+        E.flops += alg; E.mle_alg += alg;
+        S.valid_count += E.scr.mr_key[FIG_MR_VCOUNT];
+    }
+    FIG_SYNC();
+}
+
+// ---------------------------------------------------------------------------------------
 // placeReads, Figbird.cpp:3022-4387.  Returns maxLikelihood in S.lik (after a barrier).
 template <bool LDS>
 FIG_D void fig_place_reads(FigEng &E, int ge, int finalize_flag, int gapoffset, int updateflag) {
@@ -901,9 +978,19 @@ FIG_D void fig_place_reads(FigEng &E, int ge, int finalize_flag, int gapoffset, 
         for (int x = E.tid; x < S.ncols; x += E.nt) E.gs[x] = E.scr.cons[x];
         FIG_SYNC();
         FIG_TICK(E, 6);
-        fig_mle_dispatch<LDS>(E, gapoffset, 0, G, left, right);
-        FIG_TICK(E, 7);
-        for (int x = E.tid; x < S.ncols; x += E.nt) for (int j = 0; j < 5; j++) E.scr.ncnt[j * cg + x] = (double)E.scr.nci[j * cg + x];
+        // the pass, or the outputs of the previous call's when the consensus has not moved (fig_mle_reuse_*, above)
+        const bool reuse = fig_mle_reuse_on(E);
+        if (reuse && fig_mle_reuse_probe(E, gapoffset)) {
+            fig_mle_reuse_restore(E);
+            FIG_TICK(E, 7);
+        } else {
+            const unsigned long long alg0 = E.mle_alg;
+            const int vc0 = S.valid_count;
+            fig_mle_dispatch<LDS>(E, gapoffset, 0, G, left, right);
+            FIG_TICK(E, 7);
+            if (reuse) fig_mle_reuse_keep(E, gapoffset, E.mle_alg - alg0, vc0);
+            for (int x = E.tid; x < S.ncols; x += E.nt) for (int j = 0; j < 5; j++) E.scr.ncnt[j * cg + x] = (double)E.scr.nci[j * cg + x];
+        }
         // ordered likelihood sum (:3852-3862): the terms are fetched wave-wide (one coalesced load per 64 reads) and then
         // added one at a time, in read order, by every lane of the first wave alike (v_readlane broadcast)
         if (E.tid < E.wsz) {

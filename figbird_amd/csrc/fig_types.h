@@ -57,6 +57,9 @@ enum FigCounter {                    // slots of FigDevBatch::counters
     FIG_CNT_NARROW = 6,              // of them, widened chunks published narrower because the launch was emptying (FIG_SCHED_LOG reports it)
     // FIG_PROF build: FigEng::prof[i] is counter PROF_LO + i below FIG_PROF_SPLIT, PROF_HI + (i - FIG_PROF_SPLIT) from it on; cycles in barriers; wave-cycles
     FIG_CNT_PROF_LO = 8, FIG_CNT_WAIT = 30, FIG_CNT_WAVE = 31, FIG_CNT_PROF_HI = 32,
+    // MLE reuse (fig_mle_reuse_probe, fig_engine_core.h): unmapped placeReads calls that asked ; of them, calls whose consensus was that of
+    // the candidate's previous call, so that the pass was skipped (FIG_SCHED_LOG reports both; speculative evaluations included)
+    FIG_CNT_MLE_ASKED = 50, FIG_CNT_MLE_REUSED = 51,
     FIG_CNT_N = 64
 };
 #define FIG_PROF_SLOTS 40

@@ -120,6 +120,7 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
         // one emulated lane = one wave of width 1, one team; the engine always runs its LDS-table code path here
         FigKernArgs A = fig_kargs_of(c, 0, 0);
         A.nteams = 1;
+        A.mle_reuse = probe_reach ? 0 : knobs.mle_reuse;      // as the library's launches (launch_kind, fig_abi.hip)
         // LDS-tiled form of a class (fig_pack.h): what the packer chose, or forced on every class by FIG_EMU_TILES=<n> so that the
         // tile logic of the E-step is exercised on small gaps too
         if (const char *ft = getenv("FIG_EMU_TILES")) {
@@ -189,6 +190,7 @@ static int emu_run(fig_ctx *ctx, fig_gap_results *out, uint8_t *probe_reach) {
     }
     if (probe_reach) return FIG_OK;
     counters[FIG_CNT_SPEC] = counters[FIG_CNT_FLOPS];      // this build reports no speculation overhead
+    if (knobs.log && knobs.mle_reuse) fprintf(stderr, "[figsched] MLE passes reused: %llu of %llu placeReads calls executed\n", counters[FIG_CNT_MLE_REUSED], counters[FIG_CNT_MLE_ASKED]);
     fig_stats_from_counters(counters, ctx->stats);
     ctx->stats.packed_bytes = K.packed_bytes(); ctx->stats.n_launches = (int)K.classes.size();
     for (int64_t g = 0; g < ng; g++) { out->filled_len[g] = fl[g]; out->gaptofill[g] = gtf[g]; }
