@@ -209,6 +209,48 @@ class Polish:
                           support_origin=f.support_origin)
 
 
+class FigReadRecruit(C.Structure):
+    _fields_ = [("ll_seed", c_double_p), ("ll_second", c_double_p), ("ll_flat", c_double_p), ("ll_gapped", c_double_p), ("score", c_double_p),
+                ("off_seed", c_i32_p), ("off_second", c_i32_p), ("n_valid", c_i32_p), ("d_end", c_i32_p), ("read_state", c_u8_p),
+                ("draw_pos", c_i32_p), ("draw_isz", c_i32_p), ("n_candidates", c_i32_p), ("n_recruited", c_i32_p), ("state", c_u8_p)]
+
+
+# fig_read_recruit::state and ::read_state (include/figbird_hip.h)
+RECRUIT_OFF, RECRUIT_ON = 0, 1
+RECRUIT_READ_OFF, RECRUIT_KEPT, RECRUIT_NONE, RECRUIT_BELOW, RECRUIT_AMBIGUOUS, RECRUIT_RECRUITED = 0, 1, 2, 3, 4, 5
+
+
+@dataclass
+class Recruit:
+    """fig_read_recruit of one call: the twelve per-read arrays are indexed like the unmapped part of draw_pos, n_candidates,
+    n_recruited and state per gap.  filled: the FillResult the call was given."""
+    ll_seed: np.ndarray
+    ll_second: np.ndarray
+    ll_flat: np.ndarray
+    ll_gapped: np.ndarray
+    score: np.ndarray
+    off_seed: np.ndarray
+    off_second: np.ndarray
+    n_valid: np.ndarray
+    d_end: np.ndarray
+    read_state: np.ndarray
+    draw_pos: np.ndarray
+    draw_isz: np.ndarray
+    n_candidates: np.ndarray
+    n_recruited: np.ndarray
+    state: np.ndarray
+    filled: Optional["FillResult"] = None
+
+    def result(self) -> "FillResult":
+        """a FillResult made by hand of the caller's strings and the merged draw planes, the partial reads' part of the planes
+        carried over unchanged: it goes straight into indel() and polish() while the batch is resident"""
+        f = self.filled
+        dpos, disz, dlen = (np.array(a, dtype=np.int32) for a in f.draw)
+        dpos[:len(self.draw_pos)] = self.draw_pos
+        disz[:len(self.draw_isz)] = self.draw_isz
+        return dc_replace(f, draw=(dpos, disz, dlen), placement=None, quality=None, indel=None, polish=None, softqual=None, recruit=None)
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -219,7 +261,7 @@ class FigStats(C.Structure):
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
            "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
            "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality", "fig_batch_placement",
-           "fig_batch_softqual", "fig_batch_indel", "fig_batch_polish", "fig_polish_apply"]
+           "fig_batch_softqual", "fig_batch_indel", "fig_batch_polish", "fig_polish_apply", "fig_batch_recruit"]
 
 _lib = None
 _host = None
@@ -264,6 +306,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "fig_batch_polish"):              # (likewise)
         lib.fig_batch_polish.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.c_int, C.POINTER(FigGapPolish)]
         lib.fig_polish_apply.argtypes = [C.POINTER(FigGapResults), C.POINTER(FigGapPolish), C.c_int64, c_u8_p]
+    if hasattr(lib, "fig_batch_recruit"):             # (likewise)
+        lib.fig_batch_recruit.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.c_double, C.POINTER(FigReadRecruit)]
     if path is None:
         _lib = lib
     return lib
@@ -321,6 +365,17 @@ def load_host_library() -> C.CDLL:
         _host.fighost_polish_remove.argtypes = [c_i32_p, C.c_int32, c_i32_p, C.c_int64]
         _host.fig_polish_apply.argtypes = [C.POINTER(FigGapResults), C.POINTER(FigGapPolish), C.c_int64, c_u8_p]
         _host.fighost_run_write_polished.argtypes = [C.c_void_p, c_i32_p, c_i64_p, C.c_char_p, c_i32_p, c_i32_p, c_i32_p, c_u8_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
+        _host.fighost_recruit_gaps_on.argtypes = [C.c_int, C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
+        _host.fighost_recruit_candidate.argtypes = [C.c_int32]
+        _host.fighost_recruit_outside.argtypes = [C.c_int32, C.c_int32]
+        _host.fighost_recruit_before.argtypes = [C.c_double, C.c_int32, C.c_double, C.c_int32]
+        _host.fighost_recruit_seeded.argtypes = [C.c_int32, C.c_double]
+        _host.fighost_recruit_score.argtypes = [C.c_double, C.c_double]; _host.fighost_recruit_score.restype = C.c_double
+        _host.fighost_recruit_rule.argtypes = [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double]
+        _host.fighost_recruit_margin_ok.argtypes = [C.c_double]
+        _host.fighost_recruit_merge.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32_p]
+        _host.fighost_recruit_char.argtypes = [C.c_int]
+        _host.fighost_run_write_recruit.argtypes = [C.c_void_p, c_i32_p, c_u8_p, c_i32_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -469,6 +524,7 @@ class FillResult:
     quality: Optional[tuple] = None        # (loglik float64 [total, 4], phred uint8 [total], state uint8 [n_gaps]) of fig_gap_quality, indexed like raw
     indel: Optional["Indel"] = None        # fig_gap_indel of the fill's strings and drawn unmapped reads, when requested
     polish: Optional["Polish"] = None      # fig_gap_polish of the fill's strings and drawn unmapped reads, when requested
+    recruit: Optional["Recruit"] = None    # fig_read_recruit of the fill's strings and undrawn unmapped reads, when requested
     softqual: Optional["SoftQual"] = None  # fig_gap_softqual of the fill's strings, when requested
 
     @property
@@ -662,6 +718,32 @@ class Engine:
         self._check(self.lib.fig_batch_polish(self.ctx, C.byref(r), org_p, int(max_rounds), C.byref(gp)), "fig_batch_polish")
         return Polish(ed[:total], gi[0][:n], gi[1][:n], dp[:nu], gi[2][:n], gi[3][:n], gi[4][:n], d[0][:n], d[1][:n], stt[:n], filled=res)
 
+    def recruit(self, res: FillResult, origin: Optional[np.ndarray] = None, min_margin: float = 0.0) -> "Recruit":
+        """fig_batch_recruit of the strings and draw planes in `res` against the resident batch; `origin` as for quality(); min_margin
+        finite and >= 0.  The buffers handed to the library start as 0xFF bytes, so that an element it failed to write shows.  `res`
+        is not changed."""
+        self._need("fig_batch_recruit", "recruit")
+        r, keep = self._filled_struct("recruit", res)
+        n, nu = self.n_gaps, self._n_ureads()
+        if len(keep[3]) < nu or len(keep[4]) < nu:
+            raise ValueError("recruit: one drawn offset and one insert size per unmapped read of the resident batch")
+        org, org_p = self._origin_arg("recruit", origin)
+        m, gm = max(nu, 1), max(n, 1)
+        d = [np.zeros(m) for _ in range(5)]
+        for a in d:
+            a.view(np.uint8)[...] = 0xFF
+        ri = [np.full(m, -1, dtype=np.int32) for _ in range(6)]
+        gi = [np.full(gm, -1, dtype=np.int32) for _ in range(2)]
+        rs = np.full(m, 0xFF, dtype=np.uint8); stt = np.full(gm, 0xFF, dtype=np.uint8)
+        rr = FigReadRecruit()
+        rr.ll_seed, rr.ll_second, rr.ll_flat, rr.ll_gapped, rr.score = (_p(a, c_double_p) for a in d)
+        rr.off_seed, rr.off_second, rr.n_valid, rr.d_end, rr.draw_pos, rr.draw_isz = (_p(a, c_i32_p) for a in ri)
+        rr.n_candidates, rr.n_recruited = (_p(a, c_i32_p) for a in gi)
+        rr.read_state = _p(rs, c_u8_p); rr.state = _p(stt, c_u8_p)
+        self._check(self.lib.fig_batch_recruit(self.ctx, C.byref(r), org_p, C.c_double(min_margin), C.byref(rr)), "fig_batch_recruit")
+        return Recruit(d[0][:nu], d[1][:nu], d[2][:nu], d[3][:nu], d[4][:nu], ri[0][:nu], ri[1][:nu], ri[2][:nu], ri[3][:nu], rs[:nu], ri[4][:nu], ri[5][:nu],
+                       gi[0][:n], gi[1][:n], stt[:n], filled=res)
+
     def quality(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: Optional["Placement"] = None, min_pq: Optional[int] = None):
         """fig_batch_quality of the strings and draw planes in `res` against the resident batch; `origin` is
         FillResult.support_origin, or None for no origin test.  Returns (loglik [total, 4], phred [total], state [n_gaps]) with
@@ -687,8 +769,12 @@ class Engine:
         self._check(self.lib.fig_batch_quality(self.ctx, C.byref(r), org_p, C.byref(gq)), "fig_batch_quality")
         return ll[:total], ph[:total], stt[:n]
 
-    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False, indel: bool = False, polish: bool = False):
-        """quality, placement, softqual, indel and polish need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+    def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False, indel: bool = False, polish: bool = False,
+                 recruit: bool = False):
+        """quality, placement, softqual, indel, polish and recruit need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+        if recruit:
+            self._need("fig_batch_recruit", "recruit=True")
+            draw = support = True
         if polish:
             self._need("fig_batch_polish", "polish=True")
             draw = support = True
@@ -727,12 +813,14 @@ class Engine:
         return plc, qual, (self.softqual(filled, filled.support_origin) if softqual else None), (self.indel(filled, filled.support_origin) if indel else None)
 
     def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-                      placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False) -> FillResult:
+                      placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False, recruit: bool = False,
+                      recruit_margin: float = 0.0) -> FillResult:
         """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins);
         placement=True likewise fills FillResult.placement (fig_batch_placement with the origins), softqual=True
         FillResult.softqual (fig_batch_softqual with the origins), indel=True FillResult.indel (fig_batch_indel with the origins),
-        polish=True FillResult.polish (fig_batch_polish with the origins)."""
-        draw, support = self._implied(support, draw, quality, placement, softqual, indel, polish)
+        polish=True FillResult.polish (fig_batch_polish with the origins), recruit=True FillResult.recruit (fig_batch_recruit with the
+        origins and recruit_margin; the other passes see the fill's own draw planes)."""
+        draw, support = self._implied(support, draw, quality, placement, softqual, indel, polish, recruit)
         n = self.n_gaps
         nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1]) if draw else None
         r, fl, gt, so, st, planes = self._result_arrays(n, self.cap, nr, draw)
@@ -770,6 +858,8 @@ class Engine:
         res.placement, res.quality, res.softqual, res.indel = self._post_fill(res, placement, quality, softqual=softqual, indel=indel)
         if polish:
             res.polish = self.polish(res, res.support_origin)
+        if recruit:
+            res.recruit = self.recruit(res, res.support_origin, recruit_margin)
         return res
 
     def free_batch(self):
@@ -800,7 +890,7 @@ class Engine:
 
     def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False, quality: bool = False,
                     keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None, softqual: bool = False, indel: bool = False,
-                    polish: bool = False, polish_rounds: int = 0) -> FillResult:
+                    polish: bool = False, polish_rounds: int = 0, recruit: bool = False, recruit_margin: float = 0.0) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
         resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
@@ -808,10 +898,12 @@ class Engine:
         fig_batch_quality before the batch is freed (field `quality`).  keep_resident=True leaves an uploaded batch resident
         for a further call.  placement=True likewise runs fig_batch_placement (field `placement`); with min_pq as well the
         quality leaves out the scored reads below that pq (Engine.quality).  softqual=True likewise runs fig_batch_softqual (field
-        `softqual`), indel=True fig_batch_indel (field `indel`), polish=True fig_batch_polish with polish_rounds (field `polish`)."""
-        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual, indel, polish)
+        `softqual`), indel=True fig_batch_indel (field `indel`), polish=True fig_batch_polish with polish_rounds (field `polish`),
+        recruit=True fig_batch_recruit with recruit_margin (field `recruit`): the indel pass and the polish then see the merged draw
+        planes (Recruit.result()), every other pass the fill's own."""
+        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual, indel, polish, recruit)
         placement = placement or min_pq is not None
-        qual = plc = sq = ind = pol = None
+        qual = plc = sq = ind = pol = rec = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         nr = n_ureads + n_preads
@@ -825,12 +917,20 @@ class Engine:
         if n > 0 and resident:
             try:
                 sup_c, sup_o = self._fill_resident_call(r, n, len(st), support)
-                if placement or quality or softqual or indel:
+                own = FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o)
+                if placement or quality or softqual or (indel and not recruit):
                     self.n_gaps = n; self._cb = cbatch
-                    plc, qual, sq, ind = self._post_fill(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), placement, quality, min_pq, softqual, indel)
+                    plc, qual, sq, ind = self._post_fill(own, placement, quality, min_pq, softqual, indel and not recruit)
+                merged = own
+                if recruit:
+                    self.n_gaps = n; self._cb = cbatch
+                    rec = self.recruit(own, sup_o, recruit_margin)
+                    merged = rec.result()
+                    if indel:
+                        ind = self.indel(merged, sup_o)
                 if polish:
                     self.n_gaps = n; self._cb = cbatch
-                    pol = self.polish(FillResult(fl, gt, None, str_off=so, raw=st, draw=(dpos, disz, dlen), support_origin=sup_o), sup_o, polish_rounds)
+                    pol = self.polish(merged, sup_o, polish_rounds)
             finally:
                 if not keep_resident:
                     self.lib.fig_batch_free(self.ctx)
@@ -854,13 +954,17 @@ class Engine:
         if polish:
             zi = np.zeros(0, dtype=np.int32)
             res.polish = pol if pol is not None else Polish(zi, zi, zi, zi, zi, zi, zi, np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.uint8), filled=res)
+        if recruit:
+            zi, zb, zd = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(0)
+            res.recruit = rec if rec is not None else Recruit(zd, zd, zd, zd, zd, zi, zi, zi, zi, zb, zi, zi, zi, zi, zb, filled=res)
         return res
 
     def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
-             placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False) -> FillResult:
+             placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False, recruit: bool = False,
+             recruit_margin: float = 0.0) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual, indel, polish)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual, indel, polish, recruit, recruit_margin)
         finally:
             self.free_batch()
 

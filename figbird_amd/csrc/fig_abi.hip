@@ -26,6 +26,7 @@
 #include "fig_softqual.h"
 #include "fig_indel.h"
 #include "fig_polish.h"
+#include "fig_recruit.h"
 
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
@@ -1428,6 +1429,101 @@ extern "C" int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *f, const in
 }
 
 extern "C" int fig_polish_apply(const fig_gap_results *filled, const fig_gap_polish *p, int64_t g, char *dst) { return fig_polish_apply_body(filled, p, g, dst); }
+
+// Recruiting of the reads the fill rejected (fig_recruit.h: the kernel; fig_recruit_host.h: which gaps are on, which reads are
+// candidates, the score, the rule and the merge).  One launch over the chunks that hold a candidate.
+extern "C" int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, double min_margin, fig_read_recruit *out) {
+    if (!out || !out->ll_seed || !out->ll_second || !out->ll_flat || !out->ll_gapped || !out->score || !out->off_seed || !out->off_second || !out->n_valid ||
+        !out->d_end || !out->read_state || !out->draw_pos || !out->draw_isz || !out->n_candidates || !out->n_recruited || !out->state) return FIG_EINVAL;
+    if (!fig_recruit_margin_ok(min_margin) || (f && !f->draw_isz)) return FIG_EINVAL;
+    FigPostFill P;
+    std::vector<double> insd;
+    FIG_TRY(P.open(ctx, f, &insd));
+    const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
+    const FigDevBatch &db = ctx->db;
+    const int L = ctx->dm.L, MI = ctx->dm.max_insert;
+    std::vector<int32_t> hlen((size_t)std::max<int64_t>(nu, 1), 0);
+    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+    // which gaps are on, which of their reads are candidates, and the bounds of what the kernel will index with
+    std::vector<int32_t> items, ncol((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<uint8_t> rstate((size_t)std::max<int64_t>(nu, 1), FIG_RECRUIT_READ_OFF);
+    int64_t gaps_on = 0, cands = 0, seeded = 0, recruited = 0, below = 0, ambiguous = 0, placements = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        const int32_t n = f->filled_len[g];
+        out->state[g] = fig_recruit_gap_on(ctx->dm.unmapped != 0, n, f->draw_len[2 * g], f->draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+        out->n_candidates[g] = 0; out->n_recruited[g] = 0;
+        if (out->state[g] != FIG_RECRUIT_ON) continue;
+        const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
+        if (P.drawn_reads(g, n, base, cnt, nu) < 0) return FIG_EINVAL;
+        gaps_on++; ncol[(size_t)g] = n;
+        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {                  // a chunk with no candidate is no work item
+            bool any = false;
+            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) {
+                const bool c = fig_recruit_candidate(f->draw_pos[base + r]);
+                rstate[(size_t)(base + r)] = c ? FIG_RECRUIT_NONE : FIG_RECRUIT_KEPT;
+                any = any || c; out->n_candidates[g] += c;
+            }
+            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
+        }
+        cands += out->n_candidates[g];
+    }
+    const double ninf = -std::numeric_limits<double>::infinity();
+    for (int64_t r = 0; r < nu; r++) {
+        out->ll_seed[r] = 0.0; out->ll_second[r] = 0.0; out->ll_flat[r] = 0.0; out->ll_gapped[r] = 0.0; out->score[r] = 0.0;
+        out->off_seed[r] = INT32_MIN; out->off_second[r] = INT32_MIN; out->n_valid[r] = 0; out->d_end[r] = 0; out->read_state[r] = rstate[(size_t)r];
+        if (rstate[(size_t)r] == FIG_RECRUIT_NONE) out->ll_seed[r] = ninf;
+        fig_recruit_merge(rstate[(size_t)r], f->draw_pos[r], f->draw_isz[r], INT32_MIN, 0, out->draw_pos[r], out->draw_isz[r]);
+    }
+    if (!items.empty()) {
+        std::vector<double> tid((size_t)(2 * L)), li((size_t)MI);
+        fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
+        fig_placement_li(MI, insd.data(), li.data());
+        FigRecruitArgs A;
+        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_pos = db.u.pos; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank;
+        A.L = L; A.Tmin = ctx->dm.Tmin; A.Tmax = ctx->dm.Tmax; A.max_insert = MI;
+        A.draw_pos = P.up(f->draw_pos, (size_t)nu);
+        A.items = P.up(items.data(), items.size());
+        A.ncol = P.up(ncol.data(), (size_t)ng);
+        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
+        A.str = P.up(f->str, (size_t)total);
+        A.tabs = P.up(P.tabs.data(), P.tabs.size());
+        A.tabs_id = P.up(tid.data(), tid.size());
+        A.li = P.up(li.data(), li.size());
+        double *dd = (double *)P.alloc((size_t)nu * 4 * sizeof(double));
+        int32_t *di = (int32_t *)P.alloc((size_t)nu * 5 * sizeof(int32_t));
+        A.ll_seed = dd; A.ll_second = dd + nu; A.ll_flat = dd + 2 * nu; A.ll_gapped = dd + 3 * nu;
+        A.off_seed = di; A.n_valid = di + nu; A.off_second = di + 2 * nu; A.d_end = di + 3 * nu; A.isz_seed = di + 4 * nu;
+        std::vector<double> hd((size_t)nu * 4);
+        std::vector<int32_t> hi((size_t)nu * 5);
+        FIG_TRY(P.run([&] { fig_recruit_launch(A, (unsigned)(items.size() / 2), ctx->stream); },
+                      [&] { const hipError_t e = P.fetch(hd.data(), dd, hd.size() * sizeof(double)); return e != hipSuccess ? e : P.fetch(hi.data(), di, hi.size() * sizeof(int32_t)); }));
+        // the kernel wrote ll_seed, off_seed and n_valid for the candidates of positive length and the rest for the seeded ones
+        for (int64_t g = 0; g < ng; g++) {
+            if (out->state[g] != FIG_RECRUIT_ON) continue;
+            for (int64_t r = P.hg[(size_t)g].uBase, e = r + P.hg[(size_t)g].nU; r < e; r++) {
+                if (rstate[(size_t)r] != FIG_RECRUIT_NONE || std::min(std::max(hlen[(size_t)r], 0), L) == 0) continue;
+                out->n_valid[r] = hi[(size_t)(nu + r)];
+                placements += out->n_valid[r];
+                if (!fig_recruit_seeded(out->n_valid[r], hd[(size_t)r])) continue;
+                seeded++;
+                out->ll_seed[r] = hd[(size_t)r]; out->ll_second[r] = hd[(size_t)(nu + r)]; out->ll_flat[r] = hd[(size_t)(2 * nu + r)]; out->ll_gapped[r] = hd[(size_t)(3 * nu + r)];
+                out->off_seed[r] = hi[(size_t)r]; out->off_second[r] = hi[(size_t)(2 * nu + r)]; out->d_end[r] = hi[(size_t)(3 * nu + r)];
+                const int32_t isz = hi[(size_t)(4 * nu + r)];
+                if (isz < 0 || isz >= MI) return FIG_EHIP;                       // (the kernel reports valid placements only)
+                out->score[r] = fig_recruit_score(li[(size_t)isz], out->ll_gapped[r]);
+                const uint8_t s = fig_recruit_rule(out->score[r], ctx->dm.cutoff, out->ll_seed[r], out->ll_second[r], min_margin);
+                out->read_state[r] = s;
+                fig_recruit_merge(s, f->draw_pos[r], f->draw_isz[r], out->off_seed[r], isz, out->draw_pos[r], out->draw_isz[r]);
+                recruited += s == FIG_RECRUIT_RECRUITED; below += s == FIG_RECRUIT_BELOW; ambiguous += s == FIG_RECRUIT_AMBIGUOUS;
+                out->n_recruited[g] += s == FIG_RECRUIT_RECRUITED;
+            }
+        }
+    }
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figrecruit] gaps on %lld of %lld, candidates %lld, seeded %lld, recruited %lld, below %lld, ambiguous %lld, placements scored %lld, kernel %.3f ms\n",
+                (long long)gaps_on, (long long)ng, (long long)cands, (long long)seeded, (long long)recruited, (long long)below, (long long)ambiguous, (long long)placements, P.ms);
+    return FIG_OK;
+}
 
 extern "C" int fig_fill_gaps(fig_ctx *ctx, const fig_gap_batch *batch, fig_gap_results *out) { return fig_fill_gaps_once(ctx, batch, out); }
 

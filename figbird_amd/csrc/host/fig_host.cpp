@@ -7,6 +7,7 @@
 #include "../fig_softqual_host.h"
 #include "../fig_indel_host.h"
 #include "../fig_polish_host.h"
+#include "../fig_recruit_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -800,6 +801,20 @@ bool write_polished(const RunArgs &a, const Batch &b, const Results &r, std::str
     });
 }
 
+bool write_recruit(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
+    std::string Q, O;
+    return write_per_gap(a, b, "gaprecruit.txt", err, [&](FILE *f, size_t g) {
+        const int64_t r0 = g < b.u_read_off.size() ? b.u_read_off[g] : 0, r1 = g + 1 < b.u_read_off.size() ? b.u_read_off[g + 1] : r0;
+        Q.clear(); O.clear();
+        for (int64_t k = r0; k < r1; k++) {
+            const uint8_t s = r.recruit_read[(size_t)k];
+            Q += fig_recruit_char(s);
+            if (s == FIG_RECRUIT_RECRUITED) { if (!O.empty()) O += ','; O += std::to_string(r.recruit_off[(size_t)k]); }
+        }
+        fprintf(f, "%d\t%d\t%d\t%s\t%s\n", r.filled_len[g], r.recruit_ncand[g], r.recruit_nrec[g], Q.c_str(), O.c_str());
+    });
+}
+
 bool write_draw(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     FILE *f = fopen((a.tmp + "draw.txt").c_str(), "w");
     if (!f) { err = "can't write draw.txt"; return false; }
@@ -1276,4 +1291,41 @@ extern "C" int fighost_run_write_polished(void *h, const int32_t *filled_len, co
         if (fig_polish_apply(&f, &p, (int64_t)g, &R.polish_str[g][0]) != polished_len[g]) { e = "gappolished.txt: the edit planes of gap " + std::to_string(g) + " do not give its polished length"; return written(false, e, err, errcap); }
     }
     return written(fighost::write_polished(r->a, r->B, R, e), e, err, errcap);
+}
+
+// ------------------------------------------------------------------ recruiting (fig_recruit_host.h)
+// FIG_RECRUIT_* of `ng` gaps: the placement's rule
+extern "C" int fighost_recruit_gaps_on(int unmapped_model, int64_t ng, const int32_t *filled_len, const int32_t *draw_len, const int32_t *origin, uint8_t *state) {
+    for (int64_t g = 0; g < ng; g++) state[g] = fig_recruit_gap_on(unmapped_model != 0, filled_len[g], draw_len[2 * g], draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+    return 0;
+}
+
+// the rules, one binding each: a candidate, the second's exclusion window, the order of two (score, offset) pairs, seeded, the score,
+// the three-way rule of a seeded candidate, the caller's margin, the merge of one read (pair_out[2]) and the writer's character
+extern "C" int fighost_recruit_candidate(int32_t draw_pos) { return fig_recruit_candidate(draw_pos) ? 1 : 0; }
+extern "C" int fighost_recruit_outside(int32_t o, int32_t off_seed) { return fig_recruit_outside(o, off_seed) ? 1 : 0; }
+extern "C" int fighost_recruit_before(double v, int32_t o, double bv, int32_t bo) { return fig_recruit_before(v, o, bv, bo) ? 1 : 0; }
+extern "C" int fighost_recruit_seeded(int32_t n_valid, double ll_seed) { return fig_recruit_seeded(n_valid, ll_seed) ? 1 : 0; }
+extern "C" double fighost_recruit_score(double li_seed, double ll_gapped) { return fig_recruit_score(li_seed, ll_gapped); }
+extern "C" int fighost_recruit_rule(double score, int32_t gap_prob_cutoff, double ll_seed, double ll_second, double min_margin) {
+    return fig_recruit_rule(score, gap_prob_cutoff, ll_seed, ll_second, min_margin);
+}
+extern "C" int fighost_recruit_margin_ok(double min_margin) { return fig_recruit_margin_ok(min_margin) ? 1 : 0; }
+extern "C" int fighost_recruit_merge(int read_state, int32_t draw_pos, int32_t draw_isz, int32_t off_seed, int32_t isz_seed, int32_t *pair_out) {
+    fig_recruit_merge((uint8_t)read_state, draw_pos, draw_isz, off_seed, isz_seed, pair_out[0], pair_out[1]);
+    return 0;
+}
+extern "C" int fighost_recruit_char(int read_state) { return fig_recruit_char((uint8_t)read_state); }
+
+// gaprecruit.txt of the WHOLE gap set (FIGFILL_RECRUIT=1): read_state and off_seed [unmapped reads] indexed like draw_pos, the two
+// counts [n_gaps]
+extern "C" int fighost_run_write_recruit(void *h, const int32_t *filled_len, const uint8_t *read_state, const int32_t *off_seed, const int32_t *n_candidates,
+                                         const int32_t *n_recruited, char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size(), nu = r->B.u_anchor_pos.size();
+    fighost::Results R = side_results(r, filled_len, nullptr);
+    R.recruit_read.assign(read_state, read_state + nu); R.recruit_off.assign(off_seed, off_seed + nu);
+    R.recruit_ncand.assign(n_candidates, n_candidates + ng); R.recruit_nrec.assign(n_recruited, n_recruited + ng);
+    std::string e;
+    return written(fighost::write_recruit(r->a, r->B, R, e), e, err, errcap);
 }

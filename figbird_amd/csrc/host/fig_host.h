@@ -101,6 +101,10 @@ struct Results {
     std::vector<std::string> polish_str;
     std::vector<int32_t> polish_len, polish_nins, polish_ndel;
     std::vector<uint8_t> polish_state;
+    // recruiting (fig_read_recruit), when asked for: FIG_RECRUIT_* of every unmapped read and its seed offset, indexed like draw_pos;
+    // the merged draw planes of the unmapped reads; candidates and recruits [n_gaps]
+    std::vector<uint8_t> recruit_read;
+    std::vector<int32_t> recruit_off, recruit_pos, recruit_isz, recruit_ncand, recruit_nrec;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
@@ -124,6 +128,10 @@ bool write_indel(const RunArgs &a, const Batch &b, const Results &r, std::string
 // gappolished.txt (no counterpart in the reference): per gap `g contig start G0 n polished_len state n_ins n_del P`, tab-separated,
 // the first five fields as in gapout.txt, state = the FIG_POLISH_* bits, P = the polished string (empty for polished_len <= 0)
 bool write_polished(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gaprecruit.txt (no counterpart in the reference): per gap `g contig start G0 n n_candidates n_recruited C O`, tab-separated, the
+// first five fields as in gapout.txt, C = one character per unmapped read of the gap ('.' kept, '+' recruited, '-' below, '='
+// ambiguous, '~' none or off), O = the offsets of the recruited reads in read order, comma-separated (empty without one)
+bool write_recruit(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // filledContigs.fa + Ncount.txt (FillGaps.cpp:708-926)
 bool write_scaffold(const RunArgs &a, const Scaffold &sc, const Batch &b, const Results &r, std::string &err);
 

@@ -19,7 +19,7 @@
 
 using namespace fighost;
 
-// Six calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
+// Seven calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
 // written against): bound weakly, and asking for what they compute without them is an error before anything is filled or written.
 extern "C" int fig_fill_resident_ex(fig_ctx *, fig_gap_results *, const fig_gap_support *) __attribute__((weak));
 extern "C" int fig_batch_quality(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_quality *) __attribute__((weak));
@@ -27,6 +27,7 @@ extern "C" int fig_batch_placement(fig_ctx *, const fig_gap_results *, const int
 extern "C" int fig_batch_softqual(fig_ctx *, const fig_gap_results *, const int32_t *, fig_read_placement *, fig_gap_softqual *) __attribute__((weak));
 extern "C" int fig_batch_indel(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_indel *) __attribute__((weak));
 extern "C" int fig_batch_polish(fig_ctx *, const fig_gap_results *, const int32_t *, int, fig_gap_polish *) __attribute__((weak));
+extern "C" int fig_batch_recruit(fig_ctx *, const fig_gap_results *, const int32_t *, double, fig_read_recruit *) __attribute__((weak));
 
 // The optional outputs: read from the environment once, in main(), and passed down.
 //   FIGFILL_SUPPORT=1    also the per-base read support and <tmp>/gapsupport.txt
@@ -36,20 +37,32 @@ extern "C" int fig_batch_polish(fig_ctx *, const fig_gap_results *, const int32_
 //   FIGFILL_INDEL=1      the fill with the support call, then fig_batch_indel, and <tmp>/gapindel.txt
 //   FIGFILL_POLISH=1     the fill with the support call, then fig_batch_polish (FIGFILL_POLISH_ROUNDS=<k>: its max_rounds), and
 //                        <tmp>/gappolished.txt; filledContigs.fa keeps the unpolished strings
+//   FIGFILL_RECRUIT=1    the fill with the support call, then fig_batch_recruit (FIGFILL_RECRUIT_MARGIN=<x>: its min_margin, default
+//                        0), and <tmp>/gaprecruit.txt; FIGFILL_INDEL and FIGFILL_POLISH then run on the merged draw plane, every
+//                        other pass and every other file sees the fill's own
 //   FIGFILL_QUALITY_MINPQ=<k> (only together with FIGFILL_QUALITY=1): the quality leaves out scored reads with pq < k
 struct Wants {
-    bool support_file = false, quality = false, placement_file = false, softquality = false, indel = false, polish = false;
+    bool support_file = false, quality = false, placement_file = false, softquality = false, indel = false, polish = false, recruit = false;
+    double recruit_margin = 0.0;
+    bool recruit_margin_bad = false;                                            // FIGFILL_RECRUIT_MARGIN is set and is no finite number >= 0
     int min_pq = -1;                                                            // -1 = not set
     int polish_rounds = 0;                                                      // 0 = the library's default
     bool placement() const { return placement_file || min_pq >= 0; }            // the call is needed for the file and for the filter
-    bool support() const { return support_file || quality || placement() || softquality || indel || polish; }
+    bool support() const { return support_file || quality || placement() || softquality || indel || polish || recruit; }
 };
 
 static Wants wants_from_env() {
     auto is1 = [](const char *name) { const char *s = getenv(name); return s && atoi(s) == 1; };
     Wants w;
     w.support_file = is1("FIGFILL_SUPPORT"); w.quality = is1("FIGFILL_QUALITY"); w.placement_file = is1("FIGFILL_PLACEMENT"); w.softquality = is1("FIGFILL_SOFTQUALITY");
-    w.indel = is1("FIGFILL_INDEL"); w.polish = is1("FIGFILL_POLISH");
+    w.indel = is1("FIGFILL_INDEL"); w.polish = is1("FIGFILL_POLISH"); w.recruit = is1("FIGFILL_RECRUIT");
+    if (const char *m = getenv("FIGFILL_RECRUIT_MARGIN")) {
+        if (w.recruit) {
+            char *e = nullptr;
+            const double v = strtod(m, &e);
+            if (e == m || *e != 0 || !(v >= 0) || v > 1.7976931348623157e308) w.recruit_margin_bad = true; else w.recruit_margin = v;
+        }
+    }
     if (const char *k = getenv("FIGFILL_POLISH_ROUNDS")) w.polish_rounds = w.polish ? atoi(k) : 0;
     const char *s = getenv("FIGFILL_QUALITY_MINPQ");
     w.min_pq = s && *s && w.quality ? atoi(s) : -1;
@@ -121,6 +134,23 @@ static int polish_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, 
     return rc;
 }
 
+// the recruiting of the undrawn reads of the fill `fr` just returned (the batch still resident): R.recruit_*; R.recruit_pos /
+// R.recruit_isz are whole draw planes, the partial reads' part the fill's own
+static int recruit_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu, double margin) {
+    const size_t m = (size_t)std::max<int64_t>(nu, 1), gm = (size_t)std::max<int64_t>(ng, 1);
+    R.recruit_read.assign(m, FIG_RECRUIT_READ_OFF); R.recruit_off.assign(m, INT32_MIN); R.recruit_ncand.assign(gm, 0); R.recruit_nrec.assign(gm, 0);
+    R.recruit_pos = R.draw_pos; R.recruit_isz = R.draw_isz;
+    std::vector<double> d(m * 5, 0.0);
+    std::vector<int32_t> i(m * 3, 0);
+    std::vector<uint8_t> st(gm, 0);
+    fig_read_recruit rc;
+    rc.ll_seed = d.data(); rc.ll_second = d.data() + m; rc.ll_flat = d.data() + 2 * m; rc.ll_gapped = d.data() + 3 * m; rc.score = d.data() + 4 * m;
+    rc.off_seed = R.recruit_off.data(); rc.off_second = i.data(); rc.n_valid = i.data() + m; rc.d_end = i.data() + 2 * m;
+    rc.read_state = R.recruit_read.data(); rc.draw_pos = R.recruit_pos.data(); rc.draw_isz = R.recruit_isz.data();
+    rc.n_candidates = R.recruit_ncand.data(); rc.n_recruited = R.recruit_nrec.data(); rc.state = st.data();
+    return fig_batch_recruit(ctx, fr, R.sup_origin.data(), margin, &rc);
+}
+
 // The fill of the batch `fb` (nu unmapped + np partial reads) resident in ctx, as both the single-device path and a shard run it:
 // R is sized, `fr` -- zeroed by the caller, who may have set its dbg_* fields -- becomes the view of R the library fills, then
 // the fill (with R.sup_counts / R.sup_origin when `w` needs the support call) and the passes beside it that `w` asks for.
@@ -147,8 +177,11 @@ static int fill_batch(fig_ctx *ctx, const fig_model *fm, const fig_gap_batch *fb
     if (!rc && w.placement()) { what = "fig_batch_placement"; rc = placement_resident(ctx, &fr, R, ng, nu); }
     if (!rc && w.quality) { what = "fig_batch_quality"; rc = quality_resident(ctx, &fr, R, ng, nu, w.min_pq); }
     if (!rc && w.softquality) { what = "fig_batch_softqual"; rc = softquality_resident(ctx, &fr, R, ng); }
-    if (!rc && w.indel) { what = "fig_batch_indel"; rc = indel_resident(ctx, &fr, R, ng, nu); }
-    if (!rc && w.polish) { what = "fig_batch_polish"; rc = polish_resident(ctx, &fr, R, ng, nu, w.polish_rounds); }
+    if (!rc && w.recruit) { what = "fig_batch_recruit"; rc = recruit_resident(ctx, &fr, R, ng, nu, w.recruit_margin); }
+    fig_gap_results fpost = fr;                              // what the indel pass and the polish see: the merged plane after a recruit
+    if (!rc && w.recruit) { fpost.draw_pos = R.recruit_pos.data(); fpost.draw_isz = R.recruit_isz.data(); }
+    if (!rc && w.indel) { what = "fig_batch_indel"; rc = indel_resident(ctx, &fpost, R, ng, nu); }
+    if (!rc && w.polish) { what = "fig_batch_polish"; rc = polish_resident(ctx, &fpost, R, ng, nu, w.polish_rounds); }
     return rc;
 }
 
@@ -157,7 +190,7 @@ static bool write_outputs(const RunArgs &a, const Scaffold &sc, const Batch &B, 
     return write_gapout(a, B, R, err) && write_draw(a, B, R, err) && write_gaploads(a, B, err) && write_scaffold(a, sc, B, R, err) &&
            (!w.support_file || write_support(a, B, R, err)) && (!w.quality || write_quality(a, B, R, err)) && (!w.placement_file || write_placement(a, B, R, err)) &&
            (!w.softquality || write_softquality(a, B, R, err)) && (!w.indel || write_indel(a, B, R, err)) &&
-           (!w.polish || write_polished(a, B, R, err));
+           (!w.polish || write_polished(a, B, R, err)) && (!w.recruit || write_recruit(a, B, R, err));
 }
 
 static int fail(const std::string &m) { fprintf(stderr, "%s\n", m.c_str()); return 1; }
@@ -250,6 +283,10 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         const size_t gm = (size_t)std::max<int64_t>(ng, 1);
         R.polish_str.assign(gm, std::string()); R.polish_len.assign(gm, 0); R.polish_nins.assign(gm, 0); R.polish_ndel.assign(gm, 0); R.polish_state.assign(gm, 0);
     }
+    if (w.recruit) {
+        R.recruit_read.assign((size_t)std::max<int64_t>(NU, 1), FIG_RECRUIT_READ_OFF); R.recruit_off.assign((size_t)std::max<int64_t>(NU, 1), INT32_MIN);
+        R.recruit_ncand.assign((size_t)std::max<int64_t>(ng, 1), 0); R.recruit_nrec.assign((size_t)std::max<int64_t>(ng, 1), 0);
+    }
     for (int64_t g = 0; g < ng; g++) {
         const ShardRun &S = runs[owner[g]]; const int64_t k = local[g];
         R.filled_len[g] = S.R.filled_len[k]; R.gaptofill[g] = S.R.gaptofill[k];
@@ -282,6 +319,10 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         if (placement) {                                  // one pq per unmapped read, in the order of the draw plane
             for (int64_t i = 0; i < nu; i++) R.place_pq[B.u_read_off[g] + i] = S.R.place_pq[S.sub.u_read_off[k] + i];
             R.place_state[g] = S.R.place_state[k];
+        }
+        if (w.recruit) {                                  // state and seed per unmapped read, in the order of the draw plane; the counts per gap
+            for (int64_t i = 0; i < nu; i++) { R.recruit_read[B.u_read_off[g] + i] = S.R.recruit_read[S.sub.u_read_off[k] + i]; R.recruit_off[B.u_read_off[g] + i] = S.R.recruit_off[S.sub.u_read_off[k] + i]; }
+            R.recruit_ncand[g] = S.R.recruit_ncand[k]; R.recruit_nrec[g] = S.R.recruit_nrec[k];
         }
         for (int64_t i = 0; i < np; i++) { R.draw_pos[NU +B.p_read_off[g] + i] = S.R.draw_pos[snu + S.sub.p_read_off[k] + i]; R.draw_isz[NU + B.p_read_off[g] + i] = S.R.draw_isz[snu + S.sub.p_read_off[k] + i]; }
     }
@@ -326,6 +367,8 @@ int main(int argc, char **argv) {
     if (w.softquality && !fig_batch_softqual) return fail("figfill: FIGFILL_SOFTQUALITY=1 needs fig_batch_softqual, which the library behind this build does not export");
     if (w.indel && !fig_batch_indel) return fail("figfill: FIGFILL_INDEL=1 needs fig_batch_indel, which the library behind this build does not export");
     if (w.polish && !fig_batch_polish) return fail("figfill: FIGFILL_POLISH=1 needs fig_batch_polish, which the library behind this build does not export");
+    if (w.recruit && !fig_batch_recruit) return fail("figfill: FIGFILL_RECRUIT=1 needs fig_batch_recruit, which the library behind this build does not export");
+    if (w.recruit_margin_bad) return fail("figfill: FIGFILL_RECRUIT_MARGIN must be a finite number >= 0");
     if (w.quality && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
     setenv("GPU_MAX_HW_QUEUES", "8", 0);                 // one hardware queue per scheduler lane; before any thread or HIP call (fig_abi.hip: fig_ctx_create)
     auto t0 = std::chrono::steady_clock::now();

@@ -53,6 +53,8 @@ PLANES = (
     ("polish", "ost", lambda r: r.polish.state, "gap", (), np.uint8, 0),
     ("polish", "oni", lambda r: r.polish.n_ins, "gap", (), np.int32, 0),
     ("polish", "ond", lambda r: r.polish.n_del, "gap", (), np.int32, 0),
+    ("recruit", "rrs", lambda r: r.recruit.read_state, "uread", (), np.uint8, api.RECRUIT_READ_OFF),
+    ("recruit", "rof", lambda r: r.recruit.off_seed, "uread", (), np.int32, np.iinfo(np.int32).min),
 )
 
 
@@ -70,9 +72,21 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     # FIGFILL_QUALITY=1): the quality leaves out the scored reads with pq < k; FIGFILL_SOFTQUALITY=1: also gapsoftquality.txt, the
     # per-base Phred summed over read placements (fig_gap_softqual); FIGFILL_INDEL=1: also gapindel.txt, the indel call per filled base
     # (fig_gap_indel); FIGFILL_POLISH=1 (FIGFILL_POLISH_ROUNDS=<k>: max_rounds): also gappolished.txt, the polished strings
-    # (fig_gap_polish): the edit planes travel, and rank 0 rebuilds the strings with the host library's fig_polish_apply
-    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality", "indel", "polish")}
-    support, quality, placement, softquality, indel, polish = on["support"], on["quality"], on["placement"], on["softquality"], on["indel"], on["polish"]
+    # (fig_gap_polish): the edit planes travel, and rank 0 rebuilds the strings with the host library's fig_polish_apply;
+    # FIGFILL_RECRUIT=1 (FIGFILL_RECRUIT_MARGIN=<x>: min_margin): also gaprecruit.txt, the undrawn reads placed with indels allowed
+    # (fig_read_recruit) -- the per-read state and seed offset travel, rank 0 counts per gap; the indel pass and the polish then run
+    # on the merged draw plane
+    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality", "indel", "polish", "recruit")}
+    support, quality, placement, softquality, indel, polish, recruit = (on[k] for k in ("support", "quality", "placement", "softquality", "indel", "polish", "recruit"))
+    recruit_margin = 0.0
+    if recruit and "FIGFILL_RECRUIT_MARGIN" in os.environ:
+        try:
+            recruit_margin = float(os.environ["FIGFILL_RECRUIT_MARGIN"])
+        except ValueError:
+            recruit_margin = float("nan")
+        if not (recruit_margin >= 0 and recruit_margin != float("inf")):
+            sys.stderr.write("figfill_mp: FIGFILL_RECRUIT_MARGIN must be a finite number >= 0\n")
+            return 1
     polish_rounds = (_env_int("FIGFILL_POLISH_ROUNDS") or 0) if polish else 0
     min_pq = _env_int("FIGFILL_QUALITY_MINPQ") if quality else None
     if min_pq is not None and min_pq < 0:
@@ -140,8 +154,8 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
             preset = np.zeros(max(n, 1), dtype=np.uint8)
             host.fighost_run_ot_presets(h, api._p(reach, api.c_u8_p), api._p(preset, api.c_u8_p))
             eng.set_ot_preset(preset[mine] if len(mine) else np.zeros(0, dtype=np.uint8))
-            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality or indel or polish, quality=quality, placement=placement, min_pq=min_pq,
-                                  softqual=softquality, indel=indel, polish=polish, polish_rounds=polish_rounds)
+            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality or indel or polish or recruit, quality=quality, placement=placement, min_pq=min_pq,
+                                  softqual=softquality, indel=indel, polish=polish, polish_rounds=polish_rounds, recruit=recruit, recruit_margin=recruit_margin)
             st = eng.stats()
             eng.close()
         except Exception as e:
@@ -213,6 +227,12 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                     wrc = host.fighost_run_write_polished(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(ps.off, api.c_i64_p), C.cast(raw.ctypes.data, C.c_char_p),
                                                           api._p(G["oed"], api.c_i32_p), api._p(G["oee"], api.c_i32_p), api._p(G["oln"], api.c_i32_p), api._p(G["ost"], api.c_u8_p),
                                                           api._p(G["oni"], api.c_i32_p), api._p(G["ond"], api.c_i32_p), err, 512)
+                if wrc == 0 and recruit:
+                    cand = np.concatenate([[0], np.cumsum((G["rrs"] != api.RECRUIT_READ_OFF) & (G["rrs"] != api.RECRUIT_KEPT))])[uo if unmapped else np.zeros(n + 1, dtype=np.int64)]
+                    recd = np.concatenate([[0], np.cumsum(G["rrs"] == api.RECRUIT_RECRUITED)])[uo if unmapped else np.zeros(n + 1, dtype=np.int64)]
+                    ncand = np.diff(cand).astype(np.int32) if n else np.zeros(1, np.int32); nrec = np.diff(recd).astype(np.int32) if n else np.zeros(1, np.int32)
+                    wrc = host.fighost_run_write_recruit(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(G["rrs"], api.c_u8_p), api._p(G["rof"], api.c_i32_p),
+                                                         api._p(ncand, api.c_i32_p), api._p(nrec, api.c_i32_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

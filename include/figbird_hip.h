@@ -429,6 +429,75 @@ typedef struct fig_gap_polish {
     uint8_t *state;         /* [n_gaps] FIG_POLISH_* bits */
 } fig_gap_polish;
 
+/* Optional recruiting of the reads the fill rejected (fig_batch_recruit): a gapped placement of every undrawn unmapped read.  The
+ * fill draws a read only when its UNGAPPED likelihood clears the run's cutoff, -log10(likelihood) < gap_prob_cutoff.  A read that
+ * spans a missing or extra base of the emitted string is a run of mismatches from the error to its end: it fails the cutoff and
+ * stays undrawn, and fig_gap_indel and fig_gap_polish, which look at drawn reads only, never see the very reads that carry the
+ * evidence.  Here every undrawn read of a gap is placed again with indels allowed, the fill's own threshold is applied to the gapped
+ * score, and the result is a draw plane that fig_batch_indel and fig_batch_polish accept as it is.  Every term not named here means
+ * what it means for fig_read_placement and fig_gap_indel: S(x), n, the placements o in [-(len-1), n-1], isz(o) and validity; Lr(o),
+ * li, lm, le, lt, lq, the index k, the skipping of bases outside ACGT; lI, lD, the band with W = 7, ll_flat, ll_gapped, d_end and its
+ * tie order.
+ *
+ * Gaps and reads.  A gap is FIG_RECRUIT_ON iff it is FIG_PLACE_ON.  A read of an on-gap with draw_pos[r] != INT32_MIN is KEPT; nothing
+ * about it is computed.  A read of an on-gap with draw_pos[r] == INT32_MIN is a CANDIDATE.
+ *
+ * Seed.  n_valid is the number of valid placements; ll_seed the greatest Lr(o) over the valid placements; off_seed the smallest o
+ * that attains it.  With no valid placement, or with ll_seed = -inf, the read is NONE and nothing further is computed: it reports
+ * n_valid, ll_seed = -inf, off_seed = INT32_MIN and the defaults below.
+ *
+ * Second.  ll_second is the greatest Lr(o) over the valid o with |o - off_seed| > W (offsets within the band are the same locus) and
+ * off_second the smallest such o that attains it; with no such o they are -inf and INT32_MIN.
+ *
+ * Band.  ll_flat, ll_gapped and d_end are those of fig_gap_indel with o* = off_seed: the same cell update, sweep and end order,
+ * forward only, no traceback.  (A valid placement is aligned under (off_seed, n), so the unaligned case does not arise.)
+ *
+ * Score.  score = li[isz(off_seed)] + ll_gapped, one IEEE addition.
+ *
+ * Rule (host), in this order:
+ *   1  BELOW unless -score < (double)gap_prob_cutoff: the fill's own test, on the gapped score;
+ *   2  else AMBIGUOUS unless ll_second is -inf or ll_seed - ll_second > min_margin (one IEEE subtraction);
+ *   3  else RECRUITED.
+ * min_margin is the caller's, finite and >= 0; 0.0 means "strictly better than any other locus".  No other value is built in.
+ *
+ * Out planes.  draw_pos[r] is the caller's offset for a KEPT read, off_seed for a RECRUITED read, else INT32_MIN; draw_isz[r] likewise
+ * the caller's value, isz(off_seed), or 0.  n_candidates[g] and n_recruited[g] count the gap's candidates and its RECRUITED reads.
+ *
+ * Defaults, written by the library whatever the buffers held.  Reads of off gaps and KEPT reads: doubles 0.0, offsets INT32_MIN,
+ * n_valid and d_end 0, read_state FIG_RECRUIT_READ_OFF or FIG_RECRUIT_KEPT, and the caller's draw values.  Off gaps: counts 0.
+ *
+ * Every double is a sum of table entries in a fixed order and every integer an exact comparison: all outputs are reproducible bit
+ * for bit.  There is no exp10 in this pass.
+ *
+ * Limits: drawn reads are not moved; the seed is ungapped, so a read with two far-apart indels may seed on the wrong side of both,
+ * and the band then finds at most a shift of 7; the support planes, draw.txt and filledContigs.fa remain the fill's; partial mode is
+ * off; everything fig_read_placement and fig_gap_indel list. */
+#define FIG_RECRUIT_OFF 0
+#define FIG_RECRUIT_ON  1
+#define FIG_RECRUIT_READ_OFF  0
+#define FIG_RECRUIT_KEPT      1
+#define FIG_RECRUIT_NONE      2
+#define FIG_RECRUIT_BELOW     3
+#define FIG_RECRUIT_AMBIGUOUS 4
+#define FIG_RECRUIT_RECRUITED 5
+typedef struct fig_read_recruit {
+    double  *ll_seed;       /* [n_ureads] */
+    double  *ll_second;     /* [n_ureads] */
+    double  *ll_flat;       /* [n_ureads] */
+    double  *ll_gapped;     /* [n_ureads] */
+    double  *score;         /* [n_ureads] */
+    int32_t *off_seed;      /* [n_ureads] */
+    int32_t *off_second;    /* [n_ureads] */
+    int32_t *n_valid;       /* [n_ureads] */
+    int32_t *d_end;         /* [n_ureads] */
+    uint8_t *read_state;    /* [n_ureads] FIG_RECRUIT_READ_OFF .. FIG_RECRUIT_RECRUITED */
+    int32_t *draw_pos;      /* [n_ureads] the merged offsets */
+    int32_t *draw_isz;      /* [n_ureads] the merged insert sizes */
+    int32_t *n_candidates;  /* [n_gaps] */
+    int32_t *n_recruited;   /* [n_gaps] */
+    uint8_t *state;         /* [n_gaps] FIG_RECRUIT_OFF / FIG_RECRUIT_ON */
+} fig_read_recruit;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -515,6 +584,14 @@ int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *filled, const int32_t 
 /* The polished string of gap g from the caller's strings and the edit planes of `p`: writes polished_len[g] bytes to dst (nothing when
  * dst is NULL) and returns that length, or a negative FIG_E* code.  Needs no context and no device. */
 int fig_polish_apply(const fig_gap_results *filled, const fig_gap_polish *p, int64_t g, char *dst);
+
+/* Recruiting of the undrawn unmapped reads of `filled` against the RESIDENT batch (see fig_read_recruit); `filled` and origin as for
+ * fig_batch_indel (draw_isz is read: it is carried into the merged plane).  FIG_EINVAL under fig_batch_indel's conditions, with
+ * draw_isz or a member of `out` NULL, or with min_margin negative, infinite or NaN.  Reads the resident batch and the model (the cutoff
+ * is the gap_prob_cutoff of the model that was set) and writes neither; the caller's `filled` is never changed.  One launch.  With
+ * FIG_SCHED_LOG set, one "[figrecruit]" line on stderr: gaps on, candidates, seeded, recruited, below, ambiguous, placements scored,
+ * HIP-event milliseconds of the kernel. */
+int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, double min_margin, fig_read_recruit *out);
 
 int fig_get_stats(const fig_ctx *ctx, fig_stats *out);
 
