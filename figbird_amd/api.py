@@ -251,6 +251,33 @@ class Recruit:
         return dc_replace(f, draw=(dpos, disz, dlen), placement=None, quality=None, indel=None, polish=None, softqual=None, recruit=None)
 
 
+class FigGapAlnqual(C.Structure):
+    _fields_ = [("loglik", c_double_p), ("depth", c_i32_p), ("agree", c_i32_p), ("skip", c_i32_p), ("phred", c_u8_p), ("ll_gapped", c_double_p),
+                ("n_ins", c_i32_p), ("n_del", c_i32_p), ("d_end", c_i32_p), ("d_start", c_i32_p), ("state", c_u8_p)]
+
+
+# fig_gap_alnqual::state (include/figbird_hip.h)
+ALNQ_OFF, ALNQ_ON = 0, 1
+
+
+@dataclass
+class AlnQual:
+    """fig_gap_alnqual of one call: the five planes are indexed like the strings (base x of gap g at str_off[g] + x), the five per-read
+    arrays like the unmapped part of draw_pos, state per gap.  filled: the FillResult the call was given."""
+    loglik: np.ndarray
+    depth: np.ndarray
+    agree: np.ndarray
+    skip: np.ndarray
+    phred: np.ndarray
+    ll_gapped: np.ndarray
+    n_ins: np.ndarray
+    n_del: np.ndarray
+    d_end: np.ndarray
+    d_start: np.ndarray
+    state: np.ndarray
+    filled: Optional["FillResult"] = None
+
+
 class FigStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("packed_bytes", C.c_int64), ("place_calls", C.c_int64), ("alg_flops", C.c_double),
@@ -261,7 +288,7 @@ class FigStats(C.Structure):
 EXPORTS = ["fig_version", "fig_strerror", "fig_ctx_create", "fig_ctx_destroy", "fig_ctx_set_model",
            "fig_results_capacity", "fig_batch_upload", "fig_fill_resident", "fig_fill_resident_ex", "fig_batch_free", "fig_fill_gaps",
            "fig_get_stats", "fig_batch_probe_reach", "fig_batch_set_ot_preset", "fig_batch_quality", "fig_batch_placement",
-           "fig_batch_softqual", "fig_batch_indel", "fig_batch_polish", "fig_polish_apply", "fig_batch_recruit"]
+           "fig_batch_softqual", "fig_batch_indel", "fig_batch_polish", "fig_polish_apply", "fig_batch_recruit", "fig_batch_alnqual"]
 
 _lib = None
 _host = None
@@ -308,6 +335,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.fig_polish_apply.argtypes = [C.POINTER(FigGapResults), C.POINTER(FigGapPolish), C.c_int64, c_u8_p]
     if hasattr(lib, "fig_batch_recruit"):             # (likewise)
         lib.fig_batch_recruit.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.c_double, C.POINTER(FigReadRecruit)]
+    if hasattr(lib, "fig_batch_alnqual"):             # (likewise)
+        lib.fig_batch_alnqual.argtypes = [C.c_void_p, C.POINTER(FigGapResults), c_i32_p, C.POINTER(FigGapAlnqual)]
     if path is None:
         _lib = lib
     return lib
@@ -376,6 +405,13 @@ def load_host_library() -> C.CDLL:
         _host.fighost_recruit_merge.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32_p]
         _host.fighost_recruit_char.argtypes = [C.c_int]
         _host.fighost_run_write_recruit.argtypes = [C.c_void_p, c_i32_p, c_u8_p, c_i32_p, c_i32_p, c_i32_p, C.c_char_p, C.c_int]
+        _host.fighost_alnqual_gaps_on.argtypes = [C.c_int, C.c_int64, c_i32_p, c_i32_p, c_i32_p, c_u8_p]
+        _host.fighost_alnqual_map_bytes.argtypes = [C.c_int]
+        _host.fighost_alnqual_nibble.argtypes = [c_u8_p, C.c_int]
+        _host.fighost_alnqual_set_nibble.argtypes = [c_u8_p, C.c_int, C.c_int]
+        _host.fighost_alnqual_flat.argtypes = [c_u8_p, C.c_int, c_i32_p]
+        _host.fighost_alnqual_span.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32_p]
+        _host.fighost_run_write_alnquality.argtypes = [C.c_void_p, c_i32_p, c_i64_p, c_u8_p, c_u8_p, C.c_char_p, C.c_int]
     return _host
 
 
@@ -525,6 +561,7 @@ class FillResult:
     indel: Optional["Indel"] = None        # fig_gap_indel of the fill's strings and drawn unmapped reads, when requested
     polish: Optional["Polish"] = None      # fig_gap_polish of the fill's strings and drawn unmapped reads, when requested
     recruit: Optional["Recruit"] = None    # fig_read_recruit of the fill's strings and undrawn unmapped reads, when requested
+    alnqual: Optional["AlnQual"] = None    # fig_gap_alnqual of the end of the chain (fill, recruit, polish), when requested
     softqual: Optional["SoftQual"] = None  # fig_gap_softqual of the fill's strings, when requested
 
     @property
@@ -744,6 +781,31 @@ class Engine:
         return Recruit(d[0][:nu], d[1][:nu], d[2][:nu], d[3][:nu], d[4][:nu], ri[0][:nu], ri[1][:nu], ri[2][:nu], ri[3][:nu], rs[:nu], ri[4][:nu], ri[5][:nu],
                        gi[0][:n], gi[1][:n], stt[:n], filled=res)
 
+    def alnqual(self, res: FillResult, origin: Optional[np.ndarray] = None) -> "AlnQual":
+        """fig_batch_alnqual of the strings and draw planes in `res` against the resident batch; `origin` as for quality().  The buffers
+        handed to the library start as 0xFF bytes, so that an element it failed to write shows.  `res` is not changed."""
+        self._need("fig_batch_alnqual", "alnqual")
+        r, keep = self._filled_struct("alnqual", res)
+        n, nu = self.n_gaps, self._n_ureads()
+        if len(keep[3]) < nu:
+            raise ValueError("alnqual: one drawn offset per unmapped read of the resident batch")
+        total = int(keep[1][n])
+        org, org_p = self._origin_arg("alnqual", origin)
+        m, t, gm = max(nu, 1), max(total, 1), max(n, 1)
+        ll = np.zeros((t, 4)); ll.view(np.uint8)[...] = 0xFF
+        lg = np.zeros(m); lg.view(np.uint8)[...] = 0xFF
+        pl = [np.full(t, -1, dtype=np.int32) for _ in range(3)]
+        ri = [np.full(m, -1, dtype=np.int32) for _ in range(4)]
+        ph = np.full(t, 0xFF, dtype=np.uint8); stt = np.full(gm, 0xFF, dtype=np.uint8)
+        aq = FigGapAlnqual()
+        aq.loglik = _p(ll, c_double_p); aq.ll_gapped = _p(lg, c_double_p)
+        aq.depth, aq.agree, aq.skip = (_p(a, c_i32_p) for a in pl)
+        aq.n_ins, aq.n_del, aq.d_end, aq.d_start = (_p(a, c_i32_p) for a in ri)
+        aq.phred = _p(ph, c_u8_p); aq.state = _p(stt, c_u8_p)
+        self._check(self.lib.fig_batch_alnqual(self.ctx, C.byref(r), org_p, C.byref(aq)), "fig_batch_alnqual")
+        return AlnQual(ll[:total], pl[0][:total], pl[1][:total], pl[2][:total], ph[:total], lg[:nu], ri[0][:nu], ri[1][:nu], ri[2][:nu], ri[3][:nu], stt[:n],
+                       filled=res)
+
     def quality(self, res: FillResult, origin: Optional[np.ndarray] = None, placement: Optional["Placement"] = None, min_pq: Optional[int] = None):
         """fig_batch_quality of the strings and draw planes in `res` against the resident batch; `origin` is
         FillResult.support_origin, or None for no origin test.  Returns (loglik [total, 4], phred [total], state [n_gaps]) with
@@ -770,10 +832,13 @@ class Engine:
         return ll[:total], ph[:total], stt[:n]
 
     def _implied(self, support: bool, draw: bool, quality: bool, placement: bool, softqual: bool = False, indel: bool = False, polish: bool = False,
-                 recruit: bool = False):
-        """quality, placement, softqual, indel, polish and recruit need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
+                 recruit: bool = False, alnqual: bool = False):
+        """quality, placement, softqual, indel, polish, recruit and alnqual need their calls, the draw planes and the support call (for the origins) -> (draw, support)"""
         if recruit:
             self._need("fig_batch_recruit", "recruit=True")
+            draw = support = True
+        if alnqual:
+            self._need("fig_batch_alnqual", "alnqual=True")
             draw = support = True
         if polish:
             self._need("fig_batch_polish", "polish=True")
@@ -814,13 +879,15 @@ class Engine:
 
     def fill_resident(self, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
                       placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False, recruit: bool = False,
-                      recruit_margin: float = 0.0) -> FillResult:
+                      recruit_margin: float = 0.0, alnqual: bool = False) -> FillResult:
         """quality=True implies draw=True and support=True and also fills FillResult.quality (fig_batch_quality with the origins);
         placement=True likewise fills FillResult.placement (fig_batch_placement with the origins), softqual=True
         FillResult.softqual (fig_batch_softqual with the origins), indel=True FillResult.indel (fig_batch_indel with the origins),
         polish=True FillResult.polish (fig_batch_polish with the origins), recruit=True FillResult.recruit (fig_batch_recruit with the
-        origins and recruit_margin; the other passes see the fill's own draw planes)."""
-        draw, support = self._implied(support, draw, quality, placement, softqual, indel, polish, recruit)
+        origins and recruit_margin; the other passes see the fill's own draw planes), alnqual=True FillResult.alnqual
+        (fig_batch_alnqual with the origins, on the end of the chain: Recruit.result() with recruit=True, Polish.result() with
+        polish=True)."""
+        draw, support = self._implied(support, draw, quality, placement, softqual, indel, polish, recruit, alnqual)
         n = self.n_gaps
         nr = int(self._batch.u_read_off[-1]) + int(self._batch.p_read_off[-1]) if draw else None
         r, fl, gt, so, st, planes = self._result_arrays(n, self.cap, nr, draw)
@@ -860,6 +927,9 @@ class Engine:
             res.polish = self.polish(res, res.support_origin)
         if recruit:
             res.recruit = self.recruit(res, res.support_origin, recruit_margin)
+        if alnqual:
+            end = res.polish.result() if polish else res.recruit.result() if recruit else res
+            res.alnqual = self.alnqual(end, res.support_origin)
         return res
 
     def free_batch(self):
@@ -890,7 +960,8 @@ class Engine:
 
     def fill_struct(self, cbatch: "FigGapBatch", n_ureads: int, n_preads: int, draw: bool = True, resident: bool = False, support: bool = False, quality: bool = False,
                     keep_resident: bool = False, placement: bool = False, min_pq: Optional[int] = None, softqual: bool = False, indel: bool = False,
-                    polish: bool = False, polish_rounds: int = 0, recruit: bool = False, recruit_margin: float = 0.0) -> FillResult:
+                    polish: bool = False, polish_rounds: int = 0, recruit: bool = False, recruit_margin: float = 0.0,
+                    alnqual: bool = False) -> FillResult:
         """fig_fill_gaps on a caller-built `fig_gap_batch` (e.g. a shard view from libfighost's run handle), with the
         per-read draw planes; returns a FillResult whose `draw` field holds (draw_pos, draw_isz, draw_len).
         resident=True: the batch was uploaded with upload_struct (fig_fill_resident + fig_batch_free).  support=True: the per-base
@@ -900,10 +971,11 @@ class Engine:
         quality leaves out the scored reads below that pq (Engine.quality).  softqual=True likewise runs fig_batch_softqual (field
         `softqual`), indel=True fig_batch_indel (field `indel`), polish=True fig_batch_polish with polish_rounds (field `polish`),
         recruit=True fig_batch_recruit with recruit_margin (field `recruit`): the indel pass and the polish then see the merged draw
-        planes (Recruit.result()), every other pass the fill's own."""
-        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual, indel, polish, recruit)
+        planes (Recruit.result()), every other pass the fill's own.  alnqual=True runs fig_batch_alnqual (field `alnqual`) on the end
+        of that chain: the merged planes after a recruit, Polish.result() after a polish."""
+        draw, support = self._implied(support, draw, quality, placement or min_pq is not None, softqual, indel, polish, recruit, alnqual)
         placement = placement or min_pq is not None
-        qual = plc = sq = ind = pol = rec = None
+        qual = plc = sq = ind = pol = rec = alq = None
         n = int(cbatch.n_gaps)
         cap = int(self.lib.fig_results_capacity(C.byref(self._cm), C.byref(cbatch))) if n > 0 else 1
         nr = n_ureads + n_preads
@@ -931,6 +1003,9 @@ class Engine:
                 if polish:
                     self.n_gaps = n; self._cb = cbatch
                     pol = self.polish(merged, sup_o, polish_rounds)
+                if alnqual:
+                    self.n_gaps = n; self._cb = cbatch
+                    alq = self.alnqual(pol.result() if polish else merged, sup_o)
             finally:
                 if not keep_resident:
                     self.lib.fig_batch_free(self.ctx)
@@ -957,14 +1032,17 @@ class Engine:
         if recruit:
             zi, zb, zd = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(0)
             res.recruit = rec if rec is not None else Recruit(zd, zd, zd, zd, zd, zi, zi, zi, zi, zb, zi, zi, zi, zi, zb, filled=res)
+        if alnqual:
+            zi, zb, zd = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(0)
+            res.alnqual = alq if alq is not None else AlnQual(np.zeros((0, 4)), zi, zi, zi, zb, zd, zi, zi, zi, zi, zb, filled=res)
         return res
 
     def fill(self, batch: GapBatch, debug_cand: int = 0, plane_cols: int = 0, plane_reads: int = 0, support: bool = False, draw: bool = False, quality: bool = False,
              placement: bool = False, softqual: bool = False, indel: bool = False, polish: bool = False, recruit: bool = False,
-             recruit_margin: float = 0.0) -> FillResult:
+             recruit_margin: float = 0.0, alnqual: bool = False) -> FillResult:
         self.upload(batch)
         try:
-            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual, indel, polish, recruit, recruit_margin)
+            return self.fill_resident(debug_cand, plane_cols, plane_reads, support, draw, quality, placement, softqual, indel, polish, recruit, recruit_margin, alnqual)
         finally:
             self.free_batch()
 

@@ -22,10 +22,10 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # -ffp-contract=off: the reference multiplies and adds separately (no FMA on its x86-64 build);
 # bit-identical pile-up weights need the same two roundings.
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wno-unused-value"]
-# the translation units of libfighip.so: the engine with its ABI, and the indel, the polish and the recruit kernel in modules of
-# their own (fig_indel.h, fig_polish.h, fig_recruit.h)
+# the translation units of libfighip.so: the engine with its ABI, and the indel, the polish, the recruit and the two alnqual kernels
+# in modules of their own (fig_indel.h, fig_polish.h, fig_recruit.h, fig_alnqual.h)
 LIB_SOURCES = [os.path.join(CSRC, "fig_abi.hip"), os.path.join(CSRC, "fig_indel_kernel.hip"), os.path.join(CSRC, "fig_polish_kernel.hip"),
-               os.path.join(CSRC, "fig_recruit_kernel.hip")]
+               os.path.join(CSRC, "fig_recruit_kernel.hip"), os.path.join(CSRC, "fig_alnqual_kernel.hip")]
 
 
 def _csrc_files():
@@ -82,7 +82,8 @@ def build_figfill(force: bool = False) -> str:
     srcs = hdrs + libs + [main_cpp, os.path.join(ROOT, "include", "figbird_hip.h"), os.path.join(CSRC, "fig_gaprules.h"),
                           os.path.join(CSRC, "fig_quality_host.h"), os.path.join(CSRC, "fig_placement_host.h"),
                           os.path.join(CSRC, "fig_softqual_host.h"), os.path.join(CSRC, "fig_indel_host.h"), os.path.join(CSRC, "fig_polish_host.h"),
-                          os.path.join(CSRC, "fig_recruit_host.h")]      # (figtool_main.cpp is built below)
+                          os.path.join(CSRC, "fig_recruit_host.h"), os.path.join(CSRC, "fig_alnqual_host.h"),
+                          os.path.join(CSRC, "fig_readstage.h"), os.path.join(CSRC, "fig_types.h")]      # (figtool_main.cpp is built below)
     common = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread"]
     if force or not _newer(FIGFILL, srcs + [LIB]):
         _run(common + ["-o", FIGFILL, main_cpp] + libs + ["-L" + LIBDIR, "-lfighip", "-Wl,-rpath,$ORIGIN/../lib"])

@@ -27,6 +27,7 @@
 #include "fig_indel.h"
 #include "fig_polish.h"
 #include "fig_recruit.h"
+#include "fig_alnqual.h"
 
 // ------------------------------------------------------------------------------------- kernel
 #ifdef FIG_PROF
@@ -1522,6 +1523,101 @@ extern "C" int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *f, const i
     if (fig_knobs_from_env(ctx->dm.unmapped).log)
         fprintf(stderr, "[figrecruit] gaps on %lld of %lld, candidates %lld, seeded %lld, recruited %lld, below %lld, ambiguous %lld, placements scored %lld, kernel %.3f ms\n",
                 (long long)gaps_on, (long long)ng, (long long)cands, (long long)seeded, (long long)recruited, (long long)below, (long long)ambiguous, (long long)placements, P.ms);
+    return FIG_OK;
+}
+
+// Per-base quality over gapped read alignments (fig_alnqual.h: the two kernels and the walk; fig_alnqual_host.h: which gaps are on,
+// the map, the span, the step of a column).  The path kernel over the chunks that hold an aligned read, then the column kernel over the
+// gaps that are on, back to back on the library's stream.
+extern "C" int fig_batch_alnqual(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_alnqual *out) {
+    if (!out || !out->loglik || !out->depth || !out->agree || !out->skip || !out->phred || !out->ll_gapped || !out->n_ins || !out->n_del || !out->d_end ||
+        !out->d_start || !out->state) return FIG_EINVAL;
+    FigPostFill P;
+    FIG_TRY(P.open(ctx, f));
+    const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
+    const FigDevBatch &db = ctx->db;
+    const int L = ctx->dm.L;
+    std::vector<int32_t> hlen((size_t)std::max<int64_t>(nu, 1), 0);
+    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+    // which gaps are on, which of their reads are aligned, and the bounds of what the kernels will index with
+    std::vector<int32_t> items, list, ncol((size_t)std::max<int64_t>(ng, 1), 0);
+    std::vector<uint8_t> aligned((size_t)std::max<int64_t>(nu, 1), 0);
+    int64_t reads = 0, events = 0, cols = 0;
+    for (int64_t g = 0; g < ng; g++) {
+        const int32_t n = f->filled_len[g];
+        out->state[g] = fig_alnqual_gap_on(ctx->dm.unmapped != 0, n, f->draw_len[2 * g], f->draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+        if (out->state[g] != FIG_ALNQ_ON) continue;
+        const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
+        if (P.drawn_reads(g, n, base, cnt, nu) < 0) return FIG_EINVAL;
+        list.push_back((int32_t)g); ncol[(size_t)g] = n; cols += n;
+        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {                  // a chunk without an aligned read is no work item
+            bool any = false;
+            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) {
+                const bool a = fig_indel_aligned(f->draw_pos[base + r], std::min(std::max(hlen[(size_t)(base + r)], 0), L), n);
+                aligned[(size_t)(base + r)] = a; any = any || a; reads += a;
+            }
+            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
+        }
+    }
+    for (int64_t r = 0; r < nu; r++) { out->ll_gapped[r] = 0.0; out->n_ins[r] = 0; out->n_del[r] = 0; out->d_end[r] = 0; out->d_start[r] = INT32_MIN; }
+    if (total > 0) memset(out->loglik, 0, (size_t)total * 4 * sizeof(double));
+    for (int64_t i = 0; i < total; i++) { out->depth[i] = 0; out->agree[i] = 0; out->skip[i] = 0; out->phred[i] = 0; }
+    float ms_path = 0, ms_col = 0;
+    if (!list.empty()) {
+        std::vector<double> tid((size_t)(2 * L));
+        fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
+        FigAlnPathArgs A;
+        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank; A.L = L;
+        A.draw_pos = P.up(f->draw_pos, (size_t)nu);
+        A.items = P.up(items.data(), items.size());
+        A.ncol = P.up(ncol.data(), (size_t)ng);
+        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
+        A.str = P.up(f->str, (size_t)total);
+        A.tabs = P.up(P.tabs.data(), P.tabs.size());
+        A.tabs_id = P.up(tid.data(), tid.size());
+        A.map = (uint32_t *)P.alloc((size_t)std::max<int64_t>(nu, 1) * FIG_ALNQ_MAPW * sizeof(uint32_t));
+        double *dd = (double *)P.alloc((size_t)std::max<int64_t>(nu, 1) * sizeof(double));
+        int32_t *di = (int32_t *)P.alloc((size_t)std::max<int64_t>(nu, 1) * 6 * sizeof(int32_t));
+        A.ll_gapped = dd; A.n_ins = di; A.n_del = di + nu; A.d_end = di + 2 * nu; A.d_start = di + 3 * nu; A.span = di + 4 * nu;
+        FigAlnColArgs B;
+        B.gaps = db.gaps; B.u_len = db.u.len; B.u_aux = db.u.aux; B.u_woff = db.u.woff; B.packed = db.packed; B.L = L;
+        B.draw_pos = A.draw_pos; B.ncol = A.ncol; B.str_off = A.str_off; B.str = A.str; B.tabs = A.tabs; B.map = A.map; B.span = A.span;
+        B.list = P.up(list.data(), list.size());
+        B.loglik = (double *)P.alloc((size_t)total * 4 * sizeof(double));
+        int32_t *dc = (int32_t *)P.alloc((size_t)total * 3 * sizeof(int32_t));                // depth | agree | skip
+        B.depth = dc; B.agree = dc + total; B.skip = dc + 2 * total;
+        std::vector<double> hd((size_t)nu);
+        std::vector<int32_t> hi((size_t)nu * 4);
+        struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) hipEventDestroy(e); } } mid;       // between the two launches
+        if (P.oom) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
+        FIG_HIP(hipEventCreate(&mid.e));
+        FIG_HIP(hipMemsetAsync(B.loglik, 0, (size_t)total * 4 * sizeof(double), ctx->stream));
+        FIG_HIP(hipMemsetAsync(dc, 0, (size_t)total * 3 * sizeof(int32_t), ctx->stream));
+        FIG_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+        if (!items.empty()) FIG_HIP(fig_alnqual_path_launch(A, (unsigned)(items.size() / 2), ctx->stream));
+        FIG_HIP(hipEventRecord(mid.e, ctx->stream));
+        FIG_HIP(fig_alnqual_column_launch(B, (unsigned)list.size(), ctx->stream));
+        FIG_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        FIG_HIP(P.fetch(out->loglik, B.loglik, (size_t)total * 4 * sizeof(double)));
+        FIG_HIP(P.fetch(out->depth, B.depth, (size_t)total * sizeof(int32_t)));
+        FIG_HIP(P.fetch(out->agree, B.agree, (size_t)total * sizeof(int32_t)));
+        FIG_HIP(P.fetch(out->skip, B.skip, (size_t)total * sizeof(int32_t)));
+        if (nu > 0) { FIG_HIP(P.fetch(hd.data(), dd, hd.size() * sizeof(double))); FIG_HIP(P.fetch(hi.data(), di, hi.size() * sizeof(int32_t))); }
+        FIG_HIP(hipStreamSynchronize(ctx->stream));
+        FIG_HIP(hipEventElapsedTime(&ms_path, ctx->ev0, mid.e));
+        FIG_HIP(hipEventElapsedTime(&ms_col, mid.e, ctx->ev1));
+        for (int64_t r = 0; r < nu; r++) {
+            if (!aligned[(size_t)r]) continue;
+            out->ll_gapped[r] = hd[(size_t)r];
+            out->n_ins[r] = hi[(size_t)r]; out->n_del[r] = hi[(size_t)(nu + r)]; out->d_end[r] = hi[(size_t)(2 * nu + r)]; out->d_start[r] = hi[(size_t)(3 * nu + r)];
+            events += out->n_ins[r] + out->n_del[r] > 0;
+        }
+        for (int32_t g : list)
+            for (int64_t i = f->str_off[g], e = f->str_off[g] + ncol[(size_t)g]; i < e; i++) out->phred[i] = fig_quality_phred(out->loglik + i * 4, f->str[i]);
+    }
+    if (fig_knobs_from_env(ctx->dm.unmapped).log)
+        fprintf(stderr, "[figalnqual] gaps on %zu of %lld, reads aligned %lld, reads with an event %lld, columns %lld, path kernel %.3f ms, column kernel %.3f ms\n",
+                list.size(), (long long)ng, (long long)reads, (long long)events, (long long)cols, ms_path, ms_col);
     return FIG_OK;
 }
 

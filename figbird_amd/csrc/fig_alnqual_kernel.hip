@@ -1,0 +1,23 @@
+// fig_alnqual_kernel.hip -- the translation unit of fig_alnqual_path_kernel and fig_alnqual_column_kernel (fig_alnqual.h; DESIGN.md
+// §5i) and their launches.  It is kept out of fig_abi.hip's module so that the machine code of the kernels there is what it was before
+// these existed.
+#include <hip/hip_runtime.h>
+#include "fig_placement_host.h"
+#include "fig_readstage.h"
+// As in fig_indel_kernel.hip: fig_placement.h is wanted for fig_placement_column and also defines fig_placement_kernel, which
+// fig_abi.hip's module owns; inside an unnamed namespace the second definition is local to this unit and nothing refers to it.
+namespace {
+#include "fig_placement.h"
+}
+#define FIG_ALNQUAL_KERNEL
+#include "fig_alnqual.h"
+
+hipError_t fig_alnqual_path_launch(const FigAlnPathArgs &A, unsigned items, hipStream_t stream) {
+    hipLaunchKernelGGL(fig_alnqual_path_kernel, dim3(items), dim3(FIG_AQ_NT), 0, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t fig_alnqual_column_launch(const FigAlnColArgs &A, unsigned gaps, hipStream_t stream) {
+    hipLaunchKernelGGL(fig_alnqual_column_kernel, dim3(gaps), dim3(FIG_AQ_NT), 0, stream, A);
+    return hipGetLastError();
+}

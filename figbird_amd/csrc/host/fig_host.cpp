@@ -8,6 +8,7 @@
 #include "../fig_indel_host.h"
 #include "../fig_polish_host.h"
 #include "../fig_recruit_host.h"
+#include "../fig_alnqual_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -760,19 +761,21 @@ bool write_support(const RunArgs &a, const Batch &b, const Results &r, std::stri
     });
 }
 
-// the two Phred-per-base files: `n state` and n characters of Phred+33
-static bool write_phred_file(const RunArgs &a, const Batch &b, const Results &r, const char *name, const std::vector<uint8_t> &phred, const std::vector<uint8_t> &state, std::string &err) {
+// the Phred-per-base files: `n state` and n characters of Phred+33; len / off: the lengths and offsets of the strings that were scored
+static bool write_phred_file(const RunArgs &a, const Batch &b, const std::vector<int32_t> &len, const std::vector<int64_t> &off, const char *name,
+                             const std::vector<uint8_t> &phred, const std::vector<uint8_t> &state, std::string &err) {
     std::string Q;
     return write_per_gap(a, b, name, err, [&](FILE *f, size_t g) {
-        const int n = r.filled_len[g];
+        const int n = len[g];
         Q.clear();
-        for (int x = 0; x < n; x++) Q += (char)(33 + phred[(size_t)r.str_off[g] + x]);
+        for (int x = 0; x < n; x++) Q += (char)(33 + phred[(size_t)off[g] + x]);
         fprintf(f, "%d\t%d\t%s\n", n, (int)state[g], Q.c_str());
     });
 }
 
-bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) { return write_phred_file(a, b, r, "gapquality.txt", r.qual_phred, r.qual_state, err); }
-bool write_softquality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) { return write_phred_file(a, b, r, "gapsoftquality.txt", r.softq_phred, r.softq_state, err); }
+bool write_quality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) { return write_phred_file(a, b, r.filled_len, r.str_off, "gapquality.txt", r.qual_phred, r.qual_state, err); }
+bool write_softquality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) { return write_phred_file(a, b, r.filled_len, r.str_off, "gapsoftquality.txt", r.softq_phred, r.softq_state, err); }
+bool write_alnquality(const RunArgs &a, const Batch &b, const Results &r, std::string &err) { return write_phred_file(a, b, r.alnq_len, r.alnq_off, "gapalnquality.txt", r.alnq_phred, r.alnq_state, err); }
 
 bool write_placement(const RunArgs &a, const Batch &b, const Results &r, std::string &err) {
     std::string Q;
@@ -1328,4 +1331,41 @@ extern "C" int fighost_run_write_recruit(void *h, const int32_t *filled_len, con
     R.recruit_ncand.assign(n_candidates, n_candidates + ng); R.recruit_nrec.assign(n_recruited, n_recruited + ng);
     std::string e;
     return written(fighost::write_recruit(r->a, r->B, R, e), e, err, errcap);
+}
+
+// ------------------------------------------------------------------ quality over gapped alignments (fig_alnqual_host.h)
+extern "C" int fighost_alnqual_gaps_on(int unmapped_model, int64_t ng, const int32_t *filled_len, const int32_t *draw_len, const int32_t *origin, uint8_t *state) {
+    for (int64_t g = 0; g < ng; g++) state[g] = fig_alnqual_gap_on(unmapped_model != 0, filled_len[g], draw_len[2 * g], draw_len[2 * g + 1], origin != nullptr, origin ? origin[g] : 0);
+    return 0;
+}
+extern "C" int fighost_alnqual_map_bytes(int len) { return fig_alnqual_map_bytes(len); }
+extern "C" int fighost_alnqual_nibble(const uint8_t *map, int c) { return fig_alnqual_nibble(map, c); }
+extern "C" int fighost_alnqual_set_nibble(uint8_t *map, int c, int v) { fig_alnqual_set_nibble(map, c, v); return 0; }
+// the flat path of a read of `len` bases into a map whose bytes in use are 0xFF; out4: {d_start, d_end, n_ins, n_del}
+extern "C" int fighost_alnqual_flat(uint8_t *map, int len, int32_t *out4) {
+    int ds, de, ni, nd;
+    fig_alnqual_flat(map, len, ds, de, ni, nd);
+    out4[0] = ds; out4[1] = de; out4[2] = ni; out4[3] = nd;
+    return 0;
+}
+// span_out: {first, last column}
+extern "C" int fighost_alnqual_span(int32_t o, int32_t len, int32_t d_start, int32_t d_end, int32_t *span_out) {
+    int lo, hi;
+    fig_alnqual_span(o, len, d_start, d_end, lo, hi);
+    span_out[0] = lo; span_out[1] = hi;
+    return 0;
+}
+
+// gapalnquality.txt of the WHOLE gap set (FIGFILL_ALNQUALITY=1): len [n_gaps] and off [n_gaps + 1] of the strings that were scored,
+// phred [off[n_gaps]] indexed by them, state [n_gaps]
+extern "C" int fighost_run_write_alnquality(void *h, const int32_t *len, const int64_t *off, const uint8_t *phred, const uint8_t *state, char *err, int errcap) {
+    Run *r = (Run *)h;
+    const size_t ng = r->B.gap_contig.size();
+    fighost::Results R;
+    R.alnq_len.assign(len, len + ng);
+    R.alnq_off.assign(off, off + ng + 1);
+    R.alnq_phred.assign(phred, phred + (size_t)off[ng]);
+    R.alnq_state.assign(state, state + ng);
+    std::string e;
+    return written(fighost::write_alnquality(r->a, r->B, R, e), e, err, errcap);
 }

@@ -101,10 +101,16 @@ struct Results {
     std::vector<std::string> polish_str;
     std::vector<int32_t> polish_len, polish_nins, polish_ndel;
     std::vector<uint8_t> polish_state;
+    std::vector<int32_t> polish_pos;                       // the shifted offsets of the unmapped reads, indexed like draw_pos (one device's fill only)
     // recruiting (fig_read_recruit), when asked for: FIG_RECRUIT_* of every unmapped read and its seed offset, indexed like draw_pos;
     // the merged draw planes of the unmapped reads; candidates and recruits [n_gaps]
     std::vector<uint8_t> recruit_read;
     std::vector<int32_t> recruit_off, recruit_pos, recruit_isz, recruit_ncand, recruit_nrec;
+    // per-base quality over gapped alignments (fig_gap_alnqual), when asked for: the length of the string it scored per gap (the
+    // polished length after a polish) and that string's offsets [n_gaps + 1], Phred indexed by them, and FIG_ALNQ_* [n_gaps]
+    std::vector<int32_t> alnq_len;
+    std::vector<int64_t> alnq_off;
+    std::vector<uint8_t> alnq_phred, alnq_state;
 };
 
 // gapout.txt (Figbird.cpp:7413 + FillGaps.cpp:140-219), draw.txt (draw_read, Figbird.cpp:2385-2427)
@@ -132,6 +138,9 @@ bool write_polished(const RunArgs &a, const Batch &b, const Results &r, std::str
 // first five fields as in gapout.txt, C = one character per unmapped read of the gap ('.' kept, '+' recruited, '-' below, '='
 // ambiguous, '~' none or off), O = the offsets of the recruited reads in read order, comma-separated (empty without one)
 bool write_recruit(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
+// gapalnquality.txt (no counterpart in the reference): gapquality.txt's format, n = the length of the string that was scored (the
+// polished length after a polish), state = FIG_ALNQ_*, Q from fig_gap_alnqual::phred
+bool write_alnquality(const RunArgs &a, const Batch &b, const Results &r, std::string &err);
 // filledContigs.fa + Ncount.txt (FillGaps.cpp:708-926)
 bool write_scaffold(const RunArgs &a, const Scaffold &sc, const Batch &b, const Results &r, std::string &err);
 

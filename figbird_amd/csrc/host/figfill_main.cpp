@@ -19,7 +19,7 @@
 
 using namespace fighost;
 
-// Seven calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
+// Eight calls of the ABI a library behind figfill may lack (the one-lane emulation of the CPU tests implements the calls it was
 // written against): bound weakly, and asking for what they compute without them is an error before anything is filled or written.
 extern "C" int fig_fill_resident_ex(fig_ctx *, fig_gap_results *, const fig_gap_support *) __attribute__((weak));
 extern "C" int fig_batch_quality(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_quality *) __attribute__((weak));
@@ -28,6 +28,7 @@ extern "C" int fig_batch_softqual(fig_ctx *, const fig_gap_results *, const int3
 extern "C" int fig_batch_indel(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_indel *) __attribute__((weak));
 extern "C" int fig_batch_polish(fig_ctx *, const fig_gap_results *, const int32_t *, int, fig_gap_polish *) __attribute__((weak));
 extern "C" int fig_batch_recruit(fig_ctx *, const fig_gap_results *, const int32_t *, double, fig_read_recruit *) __attribute__((weak));
+extern "C" int fig_batch_alnqual(fig_ctx *, const fig_gap_results *, const int32_t *, fig_gap_alnqual *) __attribute__((weak));
 
 // The optional outputs: read from the environment once, in main(), and passed down.
 //   FIGFILL_SUPPORT=1    also the per-base read support and <tmp>/gapsupport.txt
@@ -40,15 +41,18 @@ extern "C" int fig_batch_recruit(fig_ctx *, const fig_gap_results *, const int32
 //   FIGFILL_RECRUIT=1    the fill with the support call, then fig_batch_recruit (FIGFILL_RECRUIT_MARGIN=<x>: its min_margin, default
 //                        0), and <tmp>/gaprecruit.txt; FIGFILL_INDEL and FIGFILL_POLISH then run on the merged draw plane, every
 //                        other pass and every other file sees the fill's own
+//   FIGFILL_ALNQUALITY=1 the fill with the support call, then fig_batch_alnqual on the end of the chain -- the fill's strings and draw
+//                        plane, the merged plane under FIGFILL_RECRUIT=1, the polished strings with the polish's shifted offsets under
+//                        FIGFILL_POLISH=1 (n is then the polished length) -- and <tmp>/gapalnquality.txt
 //   FIGFILL_QUALITY_MINPQ=<k> (only together with FIGFILL_QUALITY=1): the quality leaves out scored reads with pq < k
 struct Wants {
-    bool support_file = false, quality = false, placement_file = false, softquality = false, indel = false, polish = false, recruit = false;
+    bool support_file = false, quality = false, placement_file = false, softquality = false, indel = false, polish = false, recruit = false, alnquality = false;
     double recruit_margin = 0.0;
     bool recruit_margin_bad = false;                                            // FIGFILL_RECRUIT_MARGIN is set and is no finite number >= 0
     int min_pq = -1;                                                            // -1 = not set
     int polish_rounds = 0;                                                      // 0 = the library's default
     bool placement() const { return placement_file || min_pq >= 0; }            // the call is needed for the file and for the filter
-    bool support() const { return support_file || quality || placement() || softquality || indel || polish || recruit; }
+    bool support() const { return support_file || quality || placement() || softquality || indel || polish || recruit || alnquality; }
 };
 
 static Wants wants_from_env() {
@@ -56,6 +60,7 @@ static Wants wants_from_env() {
     Wants w;
     w.support_file = is1("FIGFILL_SUPPORT"); w.quality = is1("FIGFILL_QUALITY"); w.placement_file = is1("FIGFILL_PLACEMENT"); w.softquality = is1("FIGFILL_SOFTQUALITY");
     w.indel = is1("FIGFILL_INDEL"); w.polish = is1("FIGFILL_POLISH"); w.recruit = is1("FIGFILL_RECRUIT");
+    w.alnquality = is1("FIGFILL_ALNQUALITY");
     if (const char *m = getenv("FIGFILL_RECRUIT_MARGIN")) {
         if (w.recruit) {
             char *e = nullptr;
@@ -119,10 +124,11 @@ static int indel_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, i
 static int polish_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu, int rounds) {
     const size_t m = (size_t)std::max<int64_t>(nu, 1), t = (size_t)std::max<int64_t>(fr->str_off[ng], 1), gm = (size_t)std::max<int64_t>(ng, 1);
     R.polish_str.assign(gm, std::string()); R.polish_len.assign(gm, 0); R.polish_nins.assign(gm, 0); R.polish_ndel.assign(gm, 0); R.polish_state.assign(gm, 0);
-    std::vector<int32_t> i(t + m + 2 * gm, 0);
+    R.polish_pos.assign(m, INT32_MIN);
+    std::vector<int32_t> i(t + 2 * gm, 0);
     std::vector<double> d(2 * gm, 0.0);
     fig_gap_polish gp;
-    gp.edit = i.data(); gp.draw_pos = i.data() + t; gp.edit_end = gp.draw_pos + m; gp.rounds = gp.edit_end + gm;
+    gp.edit = i.data(); gp.draw_pos = R.polish_pos.data(); gp.edit_end = i.data() + t; gp.rounds = gp.edit_end + gm;
     gp.polished_len = R.polish_len.data(); gp.n_ins = R.polish_nins.data(); gp.n_del = R.polish_ndel.data();
     gp.ll_before = d.data(); gp.ll_after = d.data() + gm; gp.state = R.polish_state.data();
     const int rc = fig_batch_polish(ctx, fr, R.sup_origin.data(), rounds, &gp);
@@ -149,6 +155,43 @@ static int recruit_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R,
     rc.read_state = R.recruit_read.data(); rc.draw_pos = R.recruit_pos.data(); rc.draw_isz = R.recruit_isz.data();
     rc.n_candidates = R.recruit_ncand.data(); rc.n_recruited = R.recruit_nrec.data(); rc.state = st.data();
     return fig_batch_recruit(ctx, fr, R.sup_origin.data(), margin, &rc);
+}
+
+// the quality over gapped alignments of `fr` (the batch still resident): R.alnq_*.  `fr` is the end of the chain: the fill's own
+// result, or that with the merged draw plane after a recruit.  After a polish the call sees a fig_gap_results made by hand of the
+// polished strings and the polish's shifted offsets, as Polish.result() of the Python binding makes it.
+static int alnqual_resident(fig_ctx *ctx, const fig_gap_results *fr, Results &R, int64_t ng, int64_t nu, int64_t nr, bool polished) {
+    const size_t m = (size_t)std::max<int64_t>(nu, 1), gm = (size_t)std::max<int64_t>(ng, 1);
+    fig_gap_results f2 = *fr;
+    std::vector<int32_t> dpos, dlen;
+    std::string str;
+    R.alnq_len.assign(fr->filled_len, fr->filled_len + ng); R.alnq_len.resize(gm, 0);
+    R.alnq_off.assign(fr->str_off, fr->str_off + ng + 1);
+    if (polished) {
+        dpos.assign(fr->draw_pos, fr->draw_pos + std::max<int64_t>(nr, 1)); dlen.assign(fr->draw_len, fr->draw_len + std::max<int64_t>(2 * ng, 1));
+        for (int64_t r = 0; r < nu; r++) dpos[(size_t)r] = R.polish_pos[(size_t)r];
+        for (int64_t g = 0; g < ng; g++) {
+            R.alnq_off[(size_t)g] = (int64_t)str.size();
+            if (R.polish_state[(size_t)g] & FIG_POLISH_ON) {
+                str += R.polish_str[(size_t)g];
+                R.alnq_len[(size_t)g] = R.polish_len[(size_t)g]; dlen[(size_t)(2 * g)] = R.polish_len[(size_t)g];
+            } else if (fr->filled_len[g] > 0) str.append(fr->str + fr->str_off[g], (size_t)fr->filled_len[g]);      // a gap that is off keeps its own bytes
+        }
+        R.alnq_off[(size_t)ng] = (int64_t)str.size();
+        if (str.empty()) str.assign(1, 'N');
+        f2.filled_len = R.alnq_len.data(); f2.str_off = R.alnq_off.data(); f2.str = &str[0]; f2.str_capacity = (int64_t)str.size();
+        f2.draw_pos = dpos.data(); f2.draw_len = dlen.data();
+    }
+    const size_t t = (size_t)std::max<int64_t>(R.alnq_off[(size_t)ng], 1);
+    R.alnq_phred.assign(t, 0); R.alnq_state.assign(gm, 0);
+    std::vector<double> d(t * 4 + m, 0.0);
+    std::vector<int32_t> i(t * 3 + m * 4, 0);
+    fig_gap_alnqual aq;
+    aq.loglik = d.data(); aq.ll_gapped = d.data() + t * 4;
+    aq.depth = i.data(); aq.agree = i.data() + t; aq.skip = i.data() + 2 * t;
+    aq.n_ins = i.data() + 3 * t; aq.n_del = aq.n_ins + m; aq.d_end = aq.n_del + m; aq.d_start = aq.d_end + m;
+    aq.phred = R.alnq_phred.data(); aq.state = R.alnq_state.data();
+    return fig_batch_alnqual(ctx, &f2, R.sup_origin.data(), &aq);
 }
 
 // The fill of the batch `fb` (nu unmapped + np partial reads) resident in ctx, as both the single-device path and a shard run it:
@@ -182,6 +225,7 @@ static int fill_batch(fig_ctx *ctx, const fig_model *fm, const fig_gap_batch *fb
     if (!rc && w.recruit) { fpost.draw_pos = R.recruit_pos.data(); fpost.draw_isz = R.recruit_isz.data(); }
     if (!rc && w.indel) { what = "fig_batch_indel"; rc = indel_resident(ctx, &fpost, R, ng, nu); }
     if (!rc && w.polish) { what = "fig_batch_polish"; rc = polish_resident(ctx, &fpost, R, ng, nu, w.polish_rounds); }
+    if (!rc && w.alnquality) { what = "fig_batch_alnqual"; rc = alnqual_resident(ctx, &fpost, R, ng, nu, nr, w.polish); }
     return rc;
 }
 
@@ -190,7 +234,8 @@ static bool write_outputs(const RunArgs &a, const Scaffold &sc, const Batch &B, 
     return write_gapout(a, B, R, err) && write_draw(a, B, R, err) && write_gaploads(a, B, err) && write_scaffold(a, sc, B, R, err) &&
            (!w.support_file || write_support(a, B, R, err)) && (!w.quality || write_quality(a, B, R, err)) && (!w.placement_file || write_placement(a, B, R, err)) &&
            (!w.softquality || write_softquality(a, B, R, err)) && (!w.indel || write_indel(a, B, R, err)) &&
-           (!w.polish || write_polished(a, B, R, err)) && (!w.recruit || write_recruit(a, B, R, err));
+           (!w.polish || write_polished(a, B, R, err)) && (!w.recruit || write_recruit(a, B, R, err)) &&
+           (!w.alnquality || write_alnquality(a, B, R, err));
 }
 
 static int fail(const std::string &m) { fprintf(stderr, "%s\n", m.c_str()); return 1; }
@@ -287,6 +332,7 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         R.recruit_read.assign((size_t)std::max<int64_t>(NU, 1), FIG_RECRUIT_READ_OFF); R.recruit_off.assign((size_t)std::max<int64_t>(NU, 1), INT32_MIN);
         R.recruit_ncand.assign((size_t)std::max<int64_t>(ng, 1), 0); R.recruit_nrec.assign((size_t)std::max<int64_t>(ng, 1), 0);
     }
+    if (w.alnquality) { R.alnq_len.assign((size_t)std::max<int64_t>(ng, 1), 0); R.alnq_off.assign((size_t)ng + 1, 0); R.alnq_state.assign((size_t)std::max<int64_t>(ng, 1), 0); }
     for (int64_t g = 0; g < ng; g++) {
         const ShardRun &S = runs[owner[g]]; const int64_t k = local[g];
         R.filled_len[g] = S.R.filled_len[k]; R.gaptofill[g] = S.R.gaptofill[k];
@@ -312,6 +358,11 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
             R.polish_str[g] = S.R.polish_str[k]; R.polish_len[g] = S.R.polish_len[k]; R.polish_nins[g] = S.R.polish_nins[k]; R.polish_ndel[g] = S.R.polish_ndel[k];
             R.polish_state[g] = S.R.polish_state[k];
         }
+        if (w.alnquality) {                               // the Phred travels with the string that was scored: its own offsets
+            R.alnq_off[g] = (int64_t)R.alnq_phred.size();
+            R.alnq_phred.insert(R.alnq_phred.end(), S.R.alnq_phred.begin() + S.R.alnq_off[k], S.R.alnq_phred.begin() + S.R.alnq_off[k + 1]);
+            R.alnq_len[g] = S.R.alnq_len[k]; R.alnq_state[g] = S.R.alnq_state[k];
+        }
         R.draw_len[2 * g] = S.R.draw_len[2 * k]; R.draw_len[2 * g + 1] = S.R.draw_len[2 * k + 1];
         const int64_t nu = B.u_read_off[g + 1] - B.u_read_off[g], np = B.p_read_off[g + 1] - B.p_read_off[g];
         const int64_t snu = (int64_t)S.sub.u_anchor_pos.size();
@@ -327,6 +378,7 @@ static int fill_multi(const std::vector<int> &devices, const RunArgs &a, const S
         for (int64_t i = 0; i < np; i++) { R.draw_pos[NU +B.p_read_off[g] + i] = S.R.draw_pos[snu + S.sub.p_read_off[k] + i]; R.draw_isz[NU + B.p_read_off[g] + i] = S.R.draw_isz[snu + S.sub.p_read_off[k] + i]; }
     }
     R.str_off[ng] = (int64_t)R.str.size();
+    if (w.alnquality) { R.alnq_off[(size_t)ng] = (int64_t)R.alnq_phred.size(); if (R.alnq_phred.empty()) R.alnq_phred.assign(1, 0); }
     if (R.str.empty()) R.str.assign(1, 'N');
     if (support && R.sup_counts.empty()) R.sup_counts.assign(5, 0);
     if (quality && R.qual_phred.empty()) R.qual_phred.assign(1, 0);
@@ -368,6 +420,7 @@ int main(int argc, char **argv) {
     if (w.indel && !fig_batch_indel) return fail("figfill: FIGFILL_INDEL=1 needs fig_batch_indel, which the library behind this build does not export");
     if (w.polish && !fig_batch_polish) return fail("figfill: FIGFILL_POLISH=1 needs fig_batch_polish, which the library behind this build does not export");
     if (w.recruit && !fig_batch_recruit) return fail("figfill: FIGFILL_RECRUIT=1 needs fig_batch_recruit, which the library behind this build does not export");
+    if (w.alnquality && !fig_batch_alnqual) return fail("figfill: FIGFILL_ALNQUALITY=1 needs fig_batch_alnqual, which the library behind this build does not export");
     if (w.recruit_margin_bad) return fail("figfill: FIGFILL_RECRUIT_MARGIN must be a finite number >= 0");
     if (w.quality && !fig_batch_quality) return fail("figfill: FIGFILL_QUALITY=1 needs fig_batch_quality, which the library behind this build does not export");
     setenv("GPU_MAX_HW_QUEUES", "8", 0);                 // one hardware queue per scheduler lane; before any thread or HIP call (fig_abi.hip: fig_ctx_create)

@@ -34,6 +34,8 @@ def _env_int(name: str):
 # The optional planes of a shard's result, described once: the switch that turns the plane on, its name on rank 0, the shard's
 # array, what it is indexed by -- "byte": the shard's string bytes, back to back in its own gap order (any trailing shape: the
 # support has five counts per byte); "gap"; "uread": the shard's unmapped reads -- and the width and the fill of the global array.
+# "abyte": the bytes of the strings fig_batch_alnqual scored, which after a polish are the polished strings -- rank 0 takes their
+# lengths from the polish's planes and scatters that plane once the others are in place.
 # They travel after the draw planes as int32 extras in this order, and rank 0 scatters them by walking the same list.
 PLANES = (
     ("support", "sup", lambda r: r.support.reshape(-1), "byte", (5,), np.int32, 0),
@@ -55,6 +57,8 @@ PLANES = (
     ("polish", "ond", lambda r: r.polish.n_del, "gap", (), np.int32, 0),
     ("recruit", "rrs", lambda r: r.recruit.read_state, "uread", (), np.uint8, api.RECRUIT_READ_OFF),
     ("recruit", "rof", lambda r: r.recruit.off_seed, "uread", (), np.int32, np.iinfo(np.int32).min),
+    ("alnquality", "aph", lambda r: r.alnqual.phred, "abyte", (), np.uint8, 0),
+    ("alnquality", "ast", lambda r: r.alnqual.state, "gap", (), np.uint8, 0),
 )
 
 
@@ -75,8 +79,10 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
     # (fig_gap_polish): the edit planes travel, and rank 0 rebuilds the strings with the host library's fig_polish_apply;
     # FIGFILL_RECRUIT=1 (FIGFILL_RECRUIT_MARGIN=<x>: min_margin): also gaprecruit.txt, the undrawn reads placed with indels allowed
     # (fig_read_recruit) -- the per-read state and seed offset travel, rank 0 counts per gap; the indel pass and the polish then run
-    # on the merged draw plane
-    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality", "indel", "polish", "recruit")}
+    # on the merged draw plane; FIGFILL_ALNQUALITY=1: also gapalnquality.txt, the per-base Phred over gapped read alignments
+    # (fig_gap_alnqual) of the end of the chain: the merged plane after a recruit, the polished strings after a polish
+    on = {sw: _env_int("FIGFILL_" + sw.upper()) == 1 for sw in ("support", "quality", "placement", "softquality", "indel", "polish", "recruit", "alnquality")}
+    alnquality = on["alnquality"]
     support, quality, placement, softquality, indel, polish, recruit = (on[k] for k in ("support", "quality", "placement", "softquality", "indel", "polish", "recruit"))
     recruit_margin = 0.0
     if recruit and "FIGFILL_RECRUIT_MARGIN" in os.environ:
@@ -154,8 +160,8 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
             preset = np.zeros(max(n, 1), dtype=np.uint8)
             host.fighost_run_ot_presets(h, api._p(reach, api.c_u8_p), api._p(preset, api.c_u8_p))
             eng.set_ot_preset(preset[mine] if len(mine) else np.zeros(0, dtype=np.uint8))
-            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality or indel or polish or recruit, quality=quality, placement=placement, min_pq=min_pq,
-                                  softqual=softquality, indel=indel, polish=polish, polish_rounds=polish_rounds, recruit=recruit, recruit_margin=recruit_margin)
+            res = eng.fill_struct(cb, int(su.value), int(sp.value), draw=True, resident=True, support=support or quality or placement or softquality or indel or polish or recruit or alnquality, quality=quality, placement=placement, min_pq=min_pq,
+                                  softqual=softquality, indel=indel, polish=polish, polish_rounds=polish_rounds, recruit=recruit, recruit_margin=recruit_margin, alnqual=alnquality)
             st = eng.stats()
             eng.close()
         except Exception as e:
@@ -183,7 +189,8 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                 g_pos = np.full(max(NU + NP, 1), np.iinfo(np.int32).min, dtype=np.int32); g_isz = np.zeros(max(NU + NP, 1), dtype=np.int32)
                 g_len = np.full(max(2 * n, 1), -1, dtype=np.int32)
                 rows = {"byte": max(int(ps.off[-1]), 1), "gap": max(n, 1), "uread": max(NU, 1)}
-                G = {name: np.full((rows[kind],) + width, fill, dtype=dt) for _, name, _, kind, width, dt, fill in PLANES}
+                G = {name: np.full((rows[kind],) + width, fill, dtype=dt) for _, name, _, kind, width, dt, fill in PLANES if kind != "abyte"}
+                late = []                    # (gap ids, plane) of the shards' "abyte" planes
                 for ids, r_len, r_pos, r_isz, *r_x in per_rank:
                     ids = np.asarray(ids, dtype=np.int64)
                     if len(ids) == 0:
@@ -200,6 +207,9 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                     g_pos[dst_u] = r_pos[:su_]; g_isz[dst_u] = r_isz[:su_]
                     dst = {"byte": idx, "gap": ids, "uread": dst_u if unmapped else dst_u[:0]}
                     for (_, name, _, kind, width, _, _), arr in zip(planes, r_x):
+                        if kind == "abyte":
+                            late.append((ids, arr))
+                            continue
                         G[name][dst[kind]] = arr.reshape((-1,) + width)[:len(dst[kind])]
                     sp_ = int(cp.sum())
                     src_p = np.arange(sp_, dtype=np.int64)
@@ -233,6 +243,21 @@ def run(argv15, backend=None, lib_path=None, device_index=None, verbose=True) ->
                     ncand = np.diff(cand).astype(np.int32) if n else np.zeros(1, np.int32); nrec = np.diff(recd).astype(np.int32) if n else np.zeros(1, np.int32)
                     wrc = host.fighost_run_write_recruit(h, api._p(fl if n else np.zeros(1, np.int32), api.c_i32_p), api._p(G["rrs"], api.c_u8_p), api._p(G["rof"], api.c_i32_p),
                                                          api._p(ncand, api.c_i32_p), api._p(nrec, api.c_i32_p), err, 512)
+                if wrc == 0 and alnquality:
+                    # the lengths of the strings that were scored, in global gap order, and their offsets
+                    alen = np.array(fl[:n], dtype=np.int32)
+                    if polish and n:
+                        pon = (G["ost"][:n] & api.POLISH_ON) != 0
+                        alen[pon] = G["oln"][:n][pon]
+                    aoff = np.zeros(n + 1, dtype=np.int64); aoff[1:] = np.cumsum(np.maximum(alen, 0))
+                    aph = np.zeros(max(int(aoff[-1]), 1), dtype=np.uint8)
+                    for ids, arr in late:
+                        ln = np.maximum(alen[ids], 0).astype(np.int64)
+                        src0 = np.cumsum(ln) - ln
+                        idx = np.repeat(aoff[ids] - src0, ln) + np.arange(int(ln.sum()), dtype=np.int64)
+                        aph[idx] = arr[:len(idx)]
+                    wrc = host.fighost_run_write_alnquality(h, api._p(alen if n else np.zeros(1, np.int32), api.c_i32_p), api._p(aoff, api.c_i64_p),
+                                                            api._p(aph, api.c_u8_p), api._p(G["ast"], api.c_u8_p), err, 512)
                 if wrc != 0:
                     sys.stderr.write(err.value.decode() + "\n")
                 if wrc == 0 and verbose:

@@ -498,6 +498,59 @@ typedef struct fig_read_recruit {
     uint8_t *state;         /* [n_gaps] FIG_RECRUIT_OFF / FIG_RECRUIT_ON */
 } fig_read_recruit;
 
+/* Optional per-base quality over gapped read alignments (fig_batch_alnqual).  fig_gap_quality puts base j of a read on column o + j:
+ * a read that spans an indel of the emitted string is then a run of mismatches from the site to its end and lowers the Phred of
+ * columns that are correct.  Here every aligned read is piled up along the best path of fig_gap_indel's band, so that each base
+ * counts on the column the alignment puts it on.  Terms not named here mean what they mean for fig_gap_quality (lm, le, lt, the
+ * index k, the Phred rule) and for fig_gap_indel: S(x), n, which gaps are on, which reads are scored and aligned, the band with
+ * W = 7, the cell update, the sweep, the end order, ll_gapped, d_end, d_start, n_ins, n_del.
+ *
+ * Gaps.  A gap is FIG_ALNQ_ON iff it is FIG_INDEL_ON.
+ *
+ * Path of an aligned read.  If ll_gapped is finite, fig_gap_indel's traceback from (len, d_end) along the back-pointers as they
+ * stand; left-normalisation concerns the reporting of events and takes no part here.  If ll_gapped is -inf, the flat path: d = 0
+ * throughout, d_start = d_end = 0, no events.
+ *
+ * Steps.  A DIAG step into cell (i, d) puts read base j = i-1 on column x = o* + j + d.  An INS step into (i, d) puts base i-1 on
+ * no column.  A DEL step into (i, d) says the read SKIPS column x = o* + i + d - 1.  DIAG steps visit strictly increasing columns:
+ * a read has at most one base on a column.  The columns of a path are o* + d_start <= x <= o* + len - 1 + d_end, and each of them
+ * carries a base of the read or is skipped by it.
+ *
+ * Planes, over the columns 0 <= x < n of a gap that is on, compacted like str:
+ *   loglik[x][b]  from 0.0, the aligned reads in ascending read index: a read with a base s in ACGT on x adds lm[k] if s == b, else
+ *                 le[k] + lt[b][s]; every + is one IEEE double addition.  These are fig_gap_quality's terms.
+ *   depth[x]      reads with an ACGT base on x
+ *   agree[x]      those of depth[x] whose base is the emitted byte; 0 under a byte outside ACGT
+ *   skip[x]       reads with a DEL step over x
+ *   phred[x]      fig_gap_quality's rule applied to loglik[x] and the emitted byte, unchanged: a column no read puts a base on has
+ *                 Phred 1 and shows in skip
+ * Per read: ll_gapped, n_ins, n_del, d_end, d_start, equal to what fig_batch_indel returns for the same input.
+ *
+ * Defaults, written by the library whatever the buffers held.  Off gaps: planes 0, Phred 0.  Unaligned reads: ll_gapped = 0.0,
+ * n_ins = n_del = d_end = 0, d_start = INT32_MIN.
+ *
+ * Every double is a sum of table entries in a fixed order: all outputs are reproducible bit for bit.  For a gap whose aligned reads
+ * all have n_ins = n_del = 0 and d_end = 0, loglik and phred are fig_gap_quality's on the same input bit for bit.
+ *
+ * Limits: the band's limits listed for fig_gap_indel; one best path per read -- no sum over alignments; inserted bases and skipped
+ * columns carry no likelihood term; reads are taken as independent and the prior is uniform, as for fig_gap_quality; partial mode
+ * is off. */
+#define FIG_ALNQ_OFF 0
+#define FIG_ALNQ_ON  1
+typedef struct fig_gap_alnqual {
+    double  *loglik;     /* [str_off[n_gaps]*4]  (str_off[g]+x)*4 + b */
+    int32_t *depth;      /* [str_off[n_gaps]] */
+    int32_t *agree;      /* [str_off[n_gaps]] */
+    int32_t *skip;       /* [str_off[n_gaps]] */
+    uint8_t *phred;      /* [str_off[n_gaps]] */
+    double  *ll_gapped;  /* [n_ureads] */
+    int32_t *n_ins;      /* [n_ureads] */
+    int32_t *n_del;      /* [n_ureads] */
+    int32_t *d_end;      /* [n_ureads] */
+    int32_t *d_start;    /* [n_ureads] */
+    uint8_t *state;      /* [n_gaps] FIG_ALNQ_* */
+} fig_gap_alnqual;
+
 /* Timing/occupancy facts of the last fig_fill_gaps call (for bench.py). */
 typedef struct fig_stats {
     double kernel_ms;                   /* HIP-event time of the fill kernels on the library's stream */
@@ -592,6 +645,14 @@ int fig_polish_apply(const fig_gap_results *filled, const fig_gap_polish *p, int
  * FIG_SCHED_LOG set, one "[figrecruit]" line on stderr: gaps on, candidates, seeded, recruited, below, ambiguous, placements scored,
  * HIP-event milliseconds of the kernel. */
 int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, double min_margin, fig_read_recruit *out);
+
+/* Per-base quality over the gapped alignments of the drawn unmapped reads of `filled` against the RESIDENT batch (see
+ * fig_gap_alnqual); `filled` and origin as for fig_batch_indel.  FIG_EINVAL under fig_batch_indel's conditions and with a NULL member
+ * of `out`.  Reads the resident batch and the model and writes neither; the caller's `filled` is never changed.  Two launches on the
+ * library's stream with no host round trip between them: the paths into per-call buffers, then the columns.  With FIG_SCHED_LOG set,
+ * one "[figalnqual]" line on stderr: gaps on, reads aligned, reads with an event, columns, HIP-event milliseconds of each of the two
+ * launches. */
+int fig_batch_alnqual(fig_ctx *ctx, const fig_gap_results *filled, const int32_t *origin, fig_gap_alnqual *out);
 
 int fig_get_stats(const fig_ctx *ctx, fig_stats *out);
 
