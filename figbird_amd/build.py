@@ -23,7 +23,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # bit-identical pile-up weights need the same two roundings.
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-Wno-unused-value"]
 # the translation units of libfighip.so: the engine with its ABI, and the indel, the polish, the recruit and the two alnqual kernels
-# in modules of their own (fig_indel.h, fig_polish.h, fig_recruit.h, fig_alnqual.h)
+# in modules of their own (fig_indel.h, fig_polish.h, fig_recruit.h, fig_alnqual.h; the band they share: fig_band.h)
 LIB_SOURCES = [os.path.join(CSRC, "fig_abi.hip"), os.path.join(CSRC, "fig_indel_kernel.hip"), os.path.join(CSRC, "fig_polish_kernel.hip"),
                os.path.join(CSRC, "fig_recruit_kernel.hip"), os.path.join(CSRC, "fig_alnqual_kernel.hip")]
 

@@ -22,6 +22,7 @@
 #include "fig_abi_host.h"
 #include "fig_quality.h"
 #include "fig_quality_host.h"
+#define FIG_PLACEMENT_KERNEL
 #include "fig_placement.h"
 #include "fig_softqual.h"
 #include "fig_indel.h"
@@ -847,6 +848,7 @@ struct FigPostFill {
     int64_t total = 0;                         // bytes of the caller's strings
     std::vector<FigDevGap> hg;                 // the gap descriptors (read ranges, anchors)
     std::vector<double> tabs;                  // lm[L] | le[L] | lt[16] of the model's e[k] / 1 - e[k] as the device holds them
+    std::vector<double> tabs_id;               // lI[L] | lD[L] (band_in)
     FigTmpBufs tmp;
     bool oom = false;
     float ms = 0;
@@ -886,6 +888,35 @@ struct FigPostFill {
         if (p && count && hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { oom = true; return nullptr; }
         return (const T *)p;
     }
+    // the lengths of the unmapped reads as the kernels clamp them, 0 .. L
+    int read_lengths(std::vector<int32_t> &hlen) {
+        const int64_t nu = ctx->n_ureads;
+        hlen.assign((size_t)std::max<int64_t>(nu, 1), 0);
+        if (nu > 0) { FIG_HIP(fetch(hlen.data(), ctx->db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+        for (int32_t &l : hlen) l = std::min(std::max(l, 0), ctx->dm.L);
+        return FIG_OK;
+    }
+    // What the four kernels that run the band read alike (fig_band.h): the resident batch, f's offsets and strings, the work items,
+    // the gaps' columns and the two table blocks.  T: whose table blocks, built once (a polish round uploads into buffers of its
+    // own and takes the call's tables)
+    void band_in(FigBandIn &B, const std::vector<int32_t> &items, const std::vector<int32_t> &ncol) { band_in(B, items, ncol, *this); }
+    void band_in(FigBandIn &B, const std::vector<int32_t> &items, const std::vector<int32_t> &ncol, FigPostFill &T) {
+        const FigDevBatch &db = ctx->db;
+        const int64_t ng = ctx->n_gaps;
+        const int L = ctx->dm.L;
+        if (T.tabs_id.empty()) {
+            T.tabs_id.resize((size_t)(2 * L));
+            fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), T.tabs_id.data(), T.tabs_id.data() + L);
+        }
+        B.gaps = db.gaps; B.u_len = db.u.len; B.u_aux = db.u.aux; B.u_woff = db.u.woff; B.packed = db.packed; B.flank = db.flank; B.L = L;
+        B.draw_pos = up(f->draw_pos, (size_t)ctx->n_ureads);
+        B.items = up(items.data(), items.size());
+        B.ncol = up(ncol.data(), (size_t)ng);
+        B.str_off = up(f->str_off, (size_t)(ng + 1));
+        B.str = up(f->str, (size_t)f->str_off[ng]);
+        B.tabs = up(T.tabs.data(), T.tabs.size());
+        B.tabs_id = up(T.tabs_id.data(), T.tabs_id.size());
+    }
     // the launch between the context's two events, then `back` (the copies to the host) and the wait; FIG_ENOMEM if an up() / alloc() failed
     template <typename Launch, typename Back> int run(Launch launch, Back back) {
         if (oom) { hipStreamSynchronize(ctx->stream); return FIG_ENOMEM; }
@@ -900,6 +931,16 @@ struct FigPostFill {
     }
 };
 #define FIG_TRY(call) do { const int _rc = (call); if (_rc != FIG_OK) return _rc; } while (0)
+
+// The work items over cnt reads: per chunk of FIG_RS_CHUNK an item {id, first read of the chunk} if of_interest(r) holds for a read r
+// of the chunk -- a chunk with no read of interest is no work item.  of_interest sees every read once, in ascending order.
+template <typename Pred> static void fig_chunk_items(std::vector<int32_t> &items, int64_t id, int64_t cnt, Pred of_interest) {
+    for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {
+        bool any = false;
+        for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) { const bool a = of_interest(r); any = any || a; }
+        if (any) { items.push_back((int32_t)id); items.push_back((int32_t)c0); }
+    }
+}
 
 // Per-base quality of a fill's strings (fig_quality.h: the kernel; fig_quality_host.h: tables, Phred, which gaps are on)
 extern "C" int fig_batch_quality(fig_ctx *ctx, const fig_gap_results *f, const int32_t *origin, fig_gap_quality *q) {
@@ -981,11 +1022,7 @@ struct FigPlacePass {
             if (drawn < 0) return FIG_EINVAL;
             gaps_on++; ncol[(size_t)g] = n; reads += drawn; cols += n;
             for (int64_t r = 0; r < cnt; r++) scored[(size_t)(base + r)] = f->draw_pos[base + r] != INT32_MIN;
-            for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {              // a chunk without a drawn read is no work item
-                bool any = false;
-                for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) any = any || scored[(size_t)(base + r)];
-                if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
-            }
+            fig_chunk_items(items, g, cnt, [&](int64_t r) { return scored[(size_t)(base + r)] != 0; });
         }
         if (items.empty()) return FIG_OK;
         A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_pos = db.u.pos; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank;
@@ -1110,10 +1147,8 @@ static int fig_indel_pass(fig_ctx *ctx, const fig_gap_results *f, const int32_t 
     FigPostFill P;
     FIG_TRY(P.open(ctx, f));
     const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
-    const FigDevBatch &db = ctx->db;
-    const int L = ctx->dm.L;
-    std::vector<int32_t> hlen((size_t)std::max<int64_t>(nu, 1), 0);
-    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+    std::vector<int32_t> hlen;
+    FIG_TRY(P.read_lengths(hlen));
     // which gaps are on, which of their reads are aligned, and the bounds of what the kernel will index with
     std::vector<int32_t> items, ncol((size_t)std::max<int64_t>(ng, 1), 0);
     std::vector<uint8_t> aligned((size_t)std::max<int64_t>(nu, 1), 0);
@@ -1125,30 +1160,18 @@ static int fig_indel_pass(fig_ctx *ctx, const fig_gap_results *f, const int32_t 
         const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
         if (P.drawn_reads(g, n, base, cnt, nu) < 0) return FIG_EINVAL;
         gaps_on++; ncol[(size_t)g] = n;
-        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {                  // a chunk without an aligned read is no work item
-            bool any = false;
-            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) {
-                const bool a = fig_indel_aligned(f->draw_pos[base + r], std::min(std::max(hlen[(size_t)(base + r)], 0), L), n);
-                aligned[(size_t)(base + r)] = a; any = any || a; reads += a;
-            }
-            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
-        }
+        fig_chunk_items(items, g, cnt, [&](int64_t r) {
+            const bool a = fig_indel_aligned(f->draw_pos[base + r], hlen[(size_t)(base + r)], n);
+            aligned[(size_t)(base + r)] = a; reads += a;
+            return a;
+        });
     }
     for (int64_t r = 0; r < nu; r++) { out->ll_flat[r] = 0.0; out->ll_gapped[r] = 0.0; out->n_ins[r] = 0; out->n_del[r] = 0; out->d_end[r] = 0; out->d_start[r] = INT32_MIN; }
     for (int64_t i = 0; i < total; i++) { out->del_reads[i] = 0; out->ins_reads[i] = 0; out->cover[i] = 0; out->call[i] = '.'; }
     for (int64_t g = 0; g < ng; g++) { out->ins_end[g] = 0; out->call_end[g] = '.'; }
     if (!items.empty()) {
-        std::vector<double> tid((size_t)(2 * L));
-        fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
         FigIndelArgs A;
-        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank; A.L = L;
-        A.draw_pos = P.up(f->draw_pos, (size_t)nu);
-        A.items = P.up(items.data(), items.size());
-        A.ncol = P.up(ncol.data(), (size_t)ng);
-        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
-        A.str = P.up(f->str, (size_t)total);
-        A.tabs = P.up(P.tabs.data(), P.tabs.size());
-        A.tabs_id = P.up(tid.data(), tid.size());
+        P.band_in(A, items, ncol);
         double *dd = (double *)P.alloc((size_t)nu * 2 * sizeof(double));
         int32_t *di = (int32_t *)P.alloc((size_t)nu * 4 * sizeof(int32_t));
         const size_t ncnt = (size_t)total * 3 + (size_t)ng;                   // del_reads | ins_reads | cover | ins_end
@@ -1209,8 +1232,6 @@ extern "C" int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *f, const in
     FigPostFill P;
     FIG_TRY(P.open(ctx, f));
     const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
-    const FigDevBatch &db = ctx->db;
-    const int L = ctx->dm.L;
     const size_t gm = (size_t)std::max<int64_t>(ng, 1), um = (size_t)std::max<int64_t>(nu, 1);
     // the buffers of an indel pass; the first runs over the caller's strings and checks them as fig_batch_indel does
     struct Pass {
@@ -1230,9 +1251,8 @@ extern "C" int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *f, const in
     float ms_indel = 0, ms_polish = 0;
     FIG_TRY(fig_indel_pass(ctx, f, origin, &I.gi, info));
     ms_indel += info.ms;
-    std::vector<int32_t> hlen(um, 0);
-    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
-    for (int64_t r = 0; r < nu; r++) hlen[(size_t)r] = std::min(std::max(hlen[(size_t)r], 0), L);
+    std::vector<int32_t> hlen;
+    FIG_TRY(P.read_lengths(hlen));
     // the working copies
     std::vector<std::string> cur(gm), calls(gm);
     std::vector<char> call_end(gm, '.');
@@ -1254,15 +1274,19 @@ extern "C" int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *f, const in
         calls[(size_t)g].assign(I.call, (size_t)f->str_off[g], (size_t)f->filled_len[g]);
         call_end[(size_t)g] = I.call_end[(size_t)g];
     }
-    std::vector<double> tid((size_t)(2 * L));
-    fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
     std::vector<int64_t> wso((size_t)ng + 1, 0);
     std::string wstr;
-    auto compact = [&] {                                          // the round's strings back to back: nothing for a gap that is off
+    // the round's strings back to back (nothing for a gap that is off) and the working copies as a fig_gap_results
+    auto working = [&] {
         wstr.clear();
         for (int64_t g = 0; g < ng; g++) { wso[(size_t)g] = (int64_t)wstr.size(); if (out->state[g] & FIG_POLISH_ON) wstr += cur[(size_t)g]; }
         wso[(size_t)ng] = (int64_t)wstr.size();
         if (wstr.empty()) wstr.push_back('N');
+        fig_gap_results wf;
+        memset(&wf, 0, sizeof(wf));
+        wf.filled_len = wlen.data(); wf.str_off = wso.data(); wf.str = &wstr[0]; wf.str_capacity = (int64_t)wstr.size();
+        wf.draw_pos = wpos.data(); wf.draw_isz = f->draw_isz; wf.draw_len = wdl.data();
+        return wf;
     };
     struct Site { int32_t x, kind; int first, m; };               // its candidates are first .. first + m - 1
     struct Saved { int64_t g; std::string str; std::vector<int32_t> pos, edit; int32_t edit_end; };
@@ -1296,35 +1320,24 @@ extern "C" int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *f, const in
         rounds_run++;
         n_cands += (int64_t)cand_off.size();
         if (cand_off.size() > (size_t)INT32_MAX / 4) return FIG_EUNSUP;
-        // a chunk with no counted read is no item
-        for (size_t c = 0; c < cand_off.size(); c++) {
-            const int64_t g = cands[4 * c], base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
+        for (size_t c = 0; c < cand_off.size(); c++) {            // a candidate's items: the chunks of its gap's reads with a counted read
+            const int64_t g = cands[4 * c], base = P.hg[(size_t)g].uBase;
             const int32_t n = (int32_t)cur[(size_t)g].size();
-            for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {
-                bool any = false;
-                for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt) && !any; r++)
-                    any = fig_polish_counted(wpos[(size_t)(base + r)], hlen[(size_t)(base + r)], n, cands[4 * c + 1], cands[4 * c + 2]);
-                if (any) { items.push_back((int32_t)c); items.push_back((int32_t)c0); }
-            }
+            fig_chunk_items(items, (int64_t)c, P.hg[(size_t)g].nU, [&](int64_t r) {
+                return fig_polish_counted(wpos[(size_t)(base + r)], hlen[(size_t)(base + r)], n, cands[4 * c + 1], cands[4 * c + 2]);
+            });
         }
         std::vector<double> sc((size_t)std::max<int64_t>(out_len, 1), 0.0);
         if (!items.empty()) {
-            compact();
-            FigPostFill Q;                                        // the round's own device buffers
-            Q.ctx = ctx; Q.f = f;
+            const fig_gap_results wf = working();
+            FigPostFill Q;                                        // the round's own device buffers, over the working copies
+            Q.ctx = ctx; Q.f = &wf;
             std::vector<int32_t> ncol(gm, 0);
             for (int64_t g = 0; g < ng; g++) if (out->state[g] & FIG_POLISH_ON) ncol[(size_t)g] = (int32_t)cur[(size_t)g].size();
             FigPolishArgs A;
-            A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank; A.L = L;
-            A.draw_pos = Q.up(wpos.data(), (size_t)nu);
-            A.items = Q.up(items.data(), items.size());
+            Q.band_in(A, items, ncol, P);
             A.cands = Q.up(cands.data(), cands.size());
             A.cand_off = Q.up(cand_off.data(), cand_off.size());
-            A.ncol = Q.up(ncol.data(), (size_t)ng);
-            A.str_off = Q.up(wso.data(), (size_t)(ng + 1));
-            A.str = Q.up(wstr.data(), wstr.size());
-            A.tabs = Q.up(P.tabs.data(), P.tabs.size());
-            A.tabs_id = Q.up(tid.data(), tid.size());
             A.out = (double *)Q.alloc((size_t)out_len * sizeof(double));
             if (A.out) FIG_HIP(hipMemsetAsync(A.out, 0, (size_t)out_len * sizeof(double), ctx->stream));
             FIG_TRY(Q.run([&] { fig_polish_launch(A, (unsigned)(items.size() / 2), ctx->stream); },
@@ -1372,12 +1385,8 @@ extern "C" int fig_batch_polish(fig_ctx *ctx, const fig_gap_results *f, const in
         }
         if (saved.empty()) break;
         // verify: the next pass over the edited strings
-        compact();
         for (int64_t g = 0; g < ng; g++) if (out->state[g] & FIG_POLISH_ON) { wlen[(size_t)g] = (int32_t)cur[(size_t)g].size(); wdl[2 * (size_t)g] = wlen[(size_t)g]; }
-        fig_gap_results wf;
-        memset(&wf, 0, sizeof(wf));
-        wf.filled_len = wlen.data(); wf.str_off = wso.data(); wf.str = &wstr[0]; wf.str_capacity = (int64_t)wstr.size();
-        wf.draw_pos = wpos.data(); wf.draw_isz = f->draw_isz; wf.draw_len = wdl.data();
+        const fig_gap_results wf = working();
         Pass V;
         V.size(um, (size_t)wso[(size_t)ng], gm);
         FIG_TRY(fig_indel_pass(ctx, &wf, origin, &V.gi, info));
@@ -1440,11 +1449,10 @@ extern "C" int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *f, const i
     FigPostFill P;
     std::vector<double> insd;
     FIG_TRY(P.open(ctx, f, &insd));
-    const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
-    const FigDevBatch &db = ctx->db;
-    const int L = ctx->dm.L, MI = ctx->dm.max_insert;
-    std::vector<int32_t> hlen((size_t)std::max<int64_t>(nu, 1), 0);
-    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+    const int64_t ng = ctx->n_gaps, nu = ctx->n_ureads;
+    const int MI = ctx->dm.max_insert;
+    std::vector<int32_t> hlen;
+    FIG_TRY(P.read_lengths(hlen));
     // which gaps are on, which of their reads are candidates, and the bounds of what the kernel will index with
     std::vector<int32_t> items, ncol((size_t)std::max<int64_t>(ng, 1), 0);
     std::vector<uint8_t> rstate((size_t)std::max<int64_t>(nu, 1), FIG_RECRUIT_READ_OFF);
@@ -1457,15 +1465,12 @@ extern "C" int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *f, const i
         const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
         if (P.drawn_reads(g, n, base, cnt, nu) < 0) return FIG_EINVAL;
         gaps_on++; ncol[(size_t)g] = n;
-        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {                  // a chunk with no candidate is no work item
-            bool any = false;
-            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) {
-                const bool c = fig_recruit_candidate(f->draw_pos[base + r]);
-                rstate[(size_t)(base + r)] = c ? FIG_RECRUIT_NONE : FIG_RECRUIT_KEPT;
-                any = any || c; out->n_candidates[g] += c;
-            }
-            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
-        }
+        fig_chunk_items(items, g, cnt, [&](int64_t r) {
+            const bool c = fig_recruit_candidate(f->draw_pos[base + r]);
+            rstate[(size_t)(base + r)] = c ? FIG_RECRUIT_NONE : FIG_RECRUIT_KEPT;
+            out->n_candidates[g] += c;
+            return c;
+        });
         cands += out->n_candidates[g];
     }
     const double ninf = -std::numeric_limits<double>::infinity();
@@ -1476,19 +1481,14 @@ extern "C" int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *f, const i
         fig_recruit_merge(rstate[(size_t)r], f->draw_pos[r], f->draw_isz[r], INT32_MIN, 0, out->draw_pos[r], out->draw_isz[r]);
     }
     if (!items.empty()) {
-        std::vector<double> tid((size_t)(2 * L)), li((size_t)MI);
-        fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
+        std::vector<double> li((size_t)MI);
         fig_placement_li(MI, insd.data(), li.data());
-        FigRecruitArgs A;
-        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_pos = db.u.pos; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank;
-        A.L = L; A.Tmin = ctx->dm.Tmin; A.Tmax = ctx->dm.Tmax; A.max_insert = MI;
-        A.draw_pos = P.up(f->draw_pos, (size_t)nu);
-        A.items = P.up(items.data(), items.size());
-        A.ncol = P.up(ncol.data(), (size_t)ng);
-        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
-        A.str = P.up(f->str, (size_t)total);
-        A.tabs = P.up(P.tabs.data(), P.tabs.size());
-        A.tabs_id = P.up(tid.data(), tid.size());
+        FigBandIn B;
+        P.band_in(B, items, ncol);
+        FigRecruitArgs A;                                         // its own member order (fig_recruit.h)
+        A.gaps = B.gaps; A.u_len = B.u_len; A.u_aux = B.u_aux; A.u_woff = B.u_woff; A.packed = B.packed; A.flank = B.flank; A.L = B.L;
+        A.draw_pos = B.draw_pos; A.items = B.items; A.ncol = B.ncol; A.str_off = B.str_off; A.str = B.str; A.tabs = B.tabs; A.tabs_id = B.tabs_id;
+        A.u_pos = ctx->db.u.pos; A.Tmin = ctx->dm.Tmin; A.Tmax = ctx->dm.Tmax; A.max_insert = MI;
         A.li = P.up(li.data(), li.size());
         double *dd = (double *)P.alloc((size_t)nu * 4 * sizeof(double));
         int32_t *di = (int32_t *)P.alloc((size_t)nu * 5 * sizeof(int32_t));
@@ -1502,7 +1502,7 @@ extern "C" int fig_batch_recruit(fig_ctx *ctx, const fig_gap_results *f, const i
         for (int64_t g = 0; g < ng; g++) {
             if (out->state[g] != FIG_RECRUIT_ON) continue;
             for (int64_t r = P.hg[(size_t)g].uBase, e = r + P.hg[(size_t)g].nU; r < e; r++) {
-                if (rstate[(size_t)r] != FIG_RECRUIT_NONE || std::min(std::max(hlen[(size_t)r], 0), L) == 0) continue;
+                if (rstate[(size_t)r] != FIG_RECRUIT_NONE || hlen[(size_t)r] == 0) continue;
                 out->n_valid[r] = hi[(size_t)(nu + r)];
                 placements += out->n_valid[r];
                 if (!fig_recruit_seeded(out->n_valid[r], hd[(size_t)r])) continue;
@@ -1535,10 +1535,8 @@ extern "C" int fig_batch_alnqual(fig_ctx *ctx, const fig_gap_results *f, const i
     FigPostFill P;
     FIG_TRY(P.open(ctx, f));
     const int64_t ng = ctx->n_gaps, total = P.total, nu = ctx->n_ureads;
-    const FigDevBatch &db = ctx->db;
-    const int L = ctx->dm.L;
-    std::vector<int32_t> hlen((size_t)std::max<int64_t>(nu, 1), 0);
-    if (nu > 0) { FIG_HIP(P.fetch(hlen.data(), db.u.len, (size_t)nu * sizeof(int32_t))); FIG_HIP(hipStreamSynchronize(ctx->stream)); }
+    std::vector<int32_t> hlen;
+    FIG_TRY(P.read_lengths(hlen));
     // which gaps are on, which of their reads are aligned, and the bounds of what the kernels will index with
     std::vector<int32_t> items, list, ncol((size_t)std::max<int64_t>(ng, 1), 0);
     std::vector<uint8_t> aligned((size_t)std::max<int64_t>(nu, 1), 0);
@@ -1550,37 +1548,25 @@ extern "C" int fig_batch_alnqual(fig_ctx *ctx, const fig_gap_results *f, const i
         const int64_t base = P.hg[(size_t)g].uBase, cnt = P.hg[(size_t)g].nU;
         if (P.drawn_reads(g, n, base, cnt, nu) < 0) return FIG_EINVAL;
         list.push_back((int32_t)g); ncol[(size_t)g] = n; cols += n;
-        for (int64_t c0 = 0; c0 < cnt; c0 += FIG_RS_CHUNK) {                  // a chunk without an aligned read is no work item
-            bool any = false;
-            for (int64_t r = c0; r < std::min<int64_t>(c0 + FIG_RS_CHUNK, cnt); r++) {
-                const bool a = fig_indel_aligned(f->draw_pos[base + r], std::min(std::max(hlen[(size_t)(base + r)], 0), L), n);
-                aligned[(size_t)(base + r)] = a; any = any || a; reads += a;
-            }
-            if (any) { items.push_back((int32_t)g); items.push_back((int32_t)c0); }
-        }
+        fig_chunk_items(items, g, cnt, [&](int64_t r) {
+            const bool a = fig_indel_aligned(f->draw_pos[base + r], hlen[(size_t)(base + r)], n);
+            aligned[(size_t)(base + r)] = a; reads += a;
+            return a;
+        });
     }
     for (int64_t r = 0; r < nu; r++) { out->ll_gapped[r] = 0.0; out->n_ins[r] = 0; out->n_del[r] = 0; out->d_end[r] = 0; out->d_start[r] = INT32_MIN; }
     if (total > 0) memset(out->loglik, 0, (size_t)total * 4 * sizeof(double));
     for (int64_t i = 0; i < total; i++) { out->depth[i] = 0; out->agree[i] = 0; out->skip[i] = 0; out->phred[i] = 0; }
     float ms_path = 0, ms_col = 0;
     if (!list.empty()) {
-        std::vector<double> tid((size_t)(2 * L));
-        fig_indel_tables(L, ctx->h_ins.data(), ctx->h_del.data(), tid.data(), tid.data() + L);
         FigAlnPathArgs A;
-        A.gaps = db.gaps; A.u_len = db.u.len; A.u_aux = db.u.aux; A.u_woff = db.u.woff; A.packed = db.packed; A.flank = db.flank; A.L = L;
-        A.draw_pos = P.up(f->draw_pos, (size_t)nu);
-        A.items = P.up(items.data(), items.size());
-        A.ncol = P.up(ncol.data(), (size_t)ng);
-        A.str_off = P.up(f->str_off, (size_t)(ng + 1));
-        A.str = P.up(f->str, (size_t)total);
-        A.tabs = P.up(P.tabs.data(), P.tabs.size());
-        A.tabs_id = P.up(tid.data(), tid.size());
+        P.band_in(A, items, ncol);
         A.map = (uint32_t *)P.alloc((size_t)std::max<int64_t>(nu, 1) * FIG_ALNQ_MAPW * sizeof(uint32_t));
         double *dd = (double *)P.alloc((size_t)std::max<int64_t>(nu, 1) * sizeof(double));
         int32_t *di = (int32_t *)P.alloc((size_t)std::max<int64_t>(nu, 1) * 6 * sizeof(int32_t));
         A.ll_gapped = dd; A.n_ins = di; A.n_del = di + nu; A.d_end = di + 2 * nu; A.d_start = di + 3 * nu; A.span = di + 4 * nu;
         FigAlnColArgs B;
-        B.gaps = db.gaps; B.u_len = db.u.len; B.u_aux = db.u.aux; B.u_woff = db.u.woff; B.packed = db.packed; B.L = L;
+        B.gaps = A.gaps; B.u_len = A.u_len; B.u_aux = A.u_aux; B.u_woff = A.u_woff; B.packed = A.packed; B.L = A.L;
         B.draw_pos = A.draw_pos; B.ncol = A.ncol; B.str_off = A.str_off; B.str = A.str; B.tabs = A.tabs; B.map = A.map; B.span = A.span;
         B.list = P.up(list.data(), list.size());
         B.loglik = (double *)P.alloc((size_t)total * 4 * sizeof(double));

@@ -1,10 +1,10 @@
 // fig_alnqual.h -- per-base quality over gapped read alignments (fig_batch_alnqual): fig_quality's planes with base j
-// of a read on the column its best band path puts it on, not on column o + j.  Two kernels.  The path kernel runs fig_indel.h's band
-// forward exactly as fig_indel_kernel does, walks the back-pointers of every aligned read once and writes which base sits on which
-// column: the read's column map, one nibble per window column (fig_alnqual_host.h), its span and the five per-read values.  The
-// column kernel is fig_quality_kernel with the map between the column and the base: a lane owns a column, the gap's reads pass through
-// LDS in ascending read index, and every sum is fig_quality's sum in fig_quality's order.  No atomics: the order of the additions is
-// part of the definition and the three counts of a column belong to its lane.
+// of a read on the column its best band path puts it on, not on column o + j.  Two kernels.  The path kernel runs fig_band.h's band
+// forward with back-pointers as fig_indel_kernel does, walks the back-pointers of every aligned read once and writes which base
+// sits on which column: the read's column map, one nibble per window column (fig_alnqual_host.h), its span and the five per-read
+// values.  The column kernel is fig_quality_kernel with the map between the column and the base: a lane owns a column, the gap's
+// reads pass through LDS in ascending read index, and every sum is fig_quality's sum in fig_quality's order.  No atomics: the
+// order of the additions is part of the definition and the three counts of a column belong to its lane.
 //
 // The walk and the step of one (column, read) pair are __host__ __device__ functions; a plain C++ build compiles the same text
 // (tests/alnqual_main.cpp).  The kernels are compiled in a translation unit of their own for fig_indel.h's reason
@@ -13,7 +13,8 @@
 #define FIG_ALNQUAL_H
 #include <stdint.h>
 #include "fig_alnqual_host.h"
-#include "fig_indel.h"
+#include "fig_band.h"
+#include "fig_placement.h"
 
 #define FIG_AQ_NT (4 * FIG_RS_CHUNK)                 // threads of a workgroup of either kernel
 
@@ -36,21 +37,8 @@ FIG_P_HD inline void fig_alnqual_walk(BP bp, MP map, int len, int d_end, int &d_
 }
 
 #ifdef __HIPCC__
-// What the path kernel reads (all device memory; every array is read through an address-space-1 view) and the arrays it writes.
-struct FigAlnPathArgs {
-    const FigDevGap *gaps;           // the resident batch's descriptors: nU, uBase, flankOff
-    const int32_t *u_len, *u_aux;
-    const int64_t *u_woff;
-    const uint32_t *packed;
-    const uint8_t *flank;
-    const int32_t *draw_pos;         // [n_ureads] drawn offset, INT32_MIN = not drawn
-    const int32_t *items;            // [gridDim.x * 2] {gap, first read of the chunk within the gap}
-    const int32_t *ncol;             // [n_gaps] bases of the gap's string
-    const int64_t *str_off;          // [n_gaps + 1] the caller's (compacted) string offsets
-    const char *str;                 // the caller's strings
-    const double *tabs;              // lm[L] | le[L] | lt[16]
-    const double *tabs_id;           // lI[L] | lD[L]
-    int32_t L;
+// What the path kernel reads (FigBandIn; items: {gap, first read of the chunk within the gap}) and the arrays it writes.
+struct FigAlnPathArgs : FigBandIn {
     uint32_t *map;                   // [n_ureads * FIG_ALNQ_MAPW]; this and the rest are written for aligned reads only
     int32_t *span;                   // [n_ureads * 2] {first, last column of the path}, not clipped to the string
     double *ll_gapped;               // [n_ureads]
@@ -85,9 +73,9 @@ typedef uint32_t __attribute__((address_space(1))) *fig_aq_gu32w;
 typedef const uint8_t __attribute__((address_space(3))) *fig_aq_lu8p;
 
 // fig_indel_kernel's mapping: one workgroup per (gap that is on, chunk of 64 of its reads), 16 reads at a time, a read's band in one
-// 16-lane row of a wave, the back-pointers of a (read, row) two ballots' slices in one LDS dword.  What differs is the end: the 16
-// lanes of a row blank the read's map in LDS, one lane takes the end and walks back into it (the flat path when every gapped path is
-// -inf), and the 16 lanes copy the map out, a dword per store.
+// 16-lane row of a wave (fig_band_forward with back-pointers).  What differs is the end: the 16 lanes of a row blank the read's map
+// in LDS, one lane takes the end and walks back into it (the flat path when every gapped path is -inf), and the 16 lanes copy the
+// map out, a dword per store.
 __global__ void __launch_bounds__(FIG_AQ_NT) fig_alnqual_path_kernel(FigAlnPathArgs A) {
     __shared__ double s_tab[FIG_RS_TAB];
     __shared__ double s_id[2 * FIG_RS_MAXL];                     // lI at 0, lD at FIG_RS_MAXL
@@ -97,7 +85,7 @@ __global__ void __launch_bounds__(FIG_AQ_NT) fig_alnqual_path_kernel(FigAlnPathA
     __shared__ uint8_t s_S[FIG_ID_GROUP][FIG_ID_WIN];            // [x - (o - 7)]
     __shared__ double s_H[FIG_ID_GROUP][FIG_ID_ROW];
     __shared__ uint32_t s_map[FIG_ID_GROUP][FIG_ALNQ_MAPW];
-    const int tid = (int)threadIdx.x, lane = tid & 63, rr = tid / FIG_ID_ROW, q = tid & (FIG_ID_ROW - 1);
+    const int tid = (int)threadIdx.x, rr = tid / FIG_ID_ROW, q = tid & (FIG_ID_ROW - 1);
     const int g = ((fig_rs_gi32p)A.items)[2 * blockIdx.x], c0 = ((fig_rs_gi32p)A.items)[2 * blockIdx.x + 1];
     fig_rs_ggapp gp = (fig_rs_ggapp)A.gaps + g;
     const int n = ((fig_rs_gi32p)A.ncol)[g];
@@ -107,7 +95,7 @@ __global__ void __launch_bounds__(FIG_AQ_NT) fig_alnqual_path_kernel(FigAlnPathA
     fig_rs_gu8p fl = (fig_rs_gu8p)A.flank + gp->flankOff;
     fig_rs_gcp str = (fig_rs_gcp)A.str + ((fig_rs_gi64p)A.str_off)[g];
     fig_rs_stage_tables(s_tab, A.tabs, L, tid, FIG_AQ_NT);
-    for (int i = tid; i < 2 * L; i += FIG_AQ_NT) s_id[i < L ? i : FIG_RS_MAXL + (i - L)] = ((fig_rs_gcdp)A.tabs_id)[i];
+    fig_band_stage_id(s_id, A.tabs_id, L, tid, FIG_AQ_NT);
     fig_rs_ldp lm = (fig_rs_ldp)&s_tab[0], le = (fig_rs_ldp)&s_tab[L], lt = (fig_rs_ldp)&s_tab[2 * FIG_RS_MAXL];
     fig_rs_ldp lI = (fig_rs_ldp)&s_id[0], lD = (fig_rs_ldp)&s_id[FIG_RS_MAXL];
     const double ninf = -__builtin_inf();
@@ -123,36 +111,10 @@ __global__ void __launch_bounds__(FIG_AQ_NT) fig_alnqual_path_kernel(FigAlnPathA
         const int o = h4.x, len = h4.y, rev = h4.z;
         const bool al = h4.w != 0;
         fig_rs_lu32p w = (fig_rs_lu32p)&s_w[r < nc ? r : 0][0];
-        if (al) for (int i = q; i < len + 2 * FIG_INDEL_W; i += FIG_ID_ROW) s_S[rr][i] = (uint8_t)fig_placement_column(o - FIG_INDEL_W + i, n, fl, str);
+        if (al) fig_band_window(&s_S[rr][0], o, len, q, [&](int x) { return fig_placement_column(x, n, fl, str); });
         for (int i = q; i < FIG_ALNQ_MAPW; i += FIG_ID_ROW) s_map[rr][i] = 0xffffffffu;
         __syncthreads();
-        int rows = al ? len : 0;                                 // the wave walks to its longest read
-        rows = max(rows, __shfl_xor(rows, 16, 64)); rows = max(rows, __shfl_xor(rows, 32, 64));
-        double h = q < FIG_INDEL_ND ? 0.0 : ninf;
-        for (int i = 1; i <= rows; i++) {
-            const bool active = al && i <= len;
-            const double up = __shfl_down(h, 1, FIG_ID_ROW);     // H(i-1, d+1); lane 14 gets the border's -inf, lane 15 itself
-            double hn = h, ld = ninf;
-            int bp = FIG_ID_DIAG;
-            if (active) {
-                int s, k;
-                const bool ok = fig_rs_base(w, len, rev, i - 1, s, k);
-                const double t = fig_indel_term((int)s_S[rr][i - 1 + q], s, k, lm, le, lt);
-                hn = fig_indel_cell(h, up, ok, t, lI[k], bp);
-                ld = lD[k];
-            }
-            const bool sweep = active && i < len && q >= 1 && q < FIG_INDEL_ND;
-            bool rose;
-            do {
-                const double below = __shfl_up(hn, 1, FIG_ID_ROW);
-                rose = sweep && fig_indel_relax(hn, below, ld);
-                if (rose) bp = FIG_ID_DEL;
-            } while (__ballot(rose));
-            const unsigned long long b_ins = __ballot(bp == FIG_ID_INS), b_del = __ballot(bp == FIG_ID_DEL);
-            if (active && q == 0) s_bp[rr][i - 1] = (uint32_t)((b_ins >> (lane & 48)) & 0xffffu) | ((uint32_t)((b_del >> (lane & 48)) & 0xffffu) << 16);
-            h = hn;
-        }
-        s_H[rr][q] = h;
+        s_H[rr][q] = fig_band_forward<true, false>((fig_rs_lu8p)&s_S[rr][0], w, al, len, rev, q, lm, le, lt, lI, lD, &s_bp[rr][0], nullptr);
         __syncthreads();
         if (al && q == 0) {
             int d_end, d_start, n_ins, n_del, lo, hi;
@@ -160,10 +122,7 @@ __global__ void __launch_bounds__(FIG_AQ_NT) fig_alnqual_path_kernel(FigAlnPathA
             const double best = fig_indel_end((fig_rs_ldp)&s_H[rr][0], d_end);
             if (best > ninf) {
                 const uint32_t *row = &s_bp[rr][0];
-                auto bpf = [row](int i, int d) {
-                    const uint32_t v = row[i - 1] >> (d + FIG_INDEL_W);
-                    return (v & 1u) ? FIG_ID_INS : (v & 0x10000u) ? FIG_ID_DEL : FIG_ID_DIAG;
-                };
+                auto bpf = [row](int i, int d) { return fig_band_bp(row, i, d); };
                 fig_alnqual_walk(bpf, map, len, d_end, d_start, n_ins, n_del);
             } else fig_alnqual_flat(map, len, d_start, d_end, n_ins, n_del);
             fig_alnqual_span(o, len, d_start, d_end, lo, hi);

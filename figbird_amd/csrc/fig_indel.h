@@ -1,66 +1,18 @@
 // fig_indel.h -- indel evidence per filled base (fig_batch_indel): every aligned read of a gap is realigned around
-// its drawn offset by a banded dynamic program (15 diagonals) against the EMITTED sequence (string + the batch's flank codes) under
-// the run's own substitution, insertion and deletion tables, the best path is traced back, its insertions and deletions are moved
-// as far left as they go, and per column the reads that ask for an edit and the reads that span the column are counted.  A cell only
-// ADDS entries of the log10 tables the host built (fig_quality_host.h, fig_indel_host.h), one IEEE double addition each, and the rest
-// is comparisons: every output is reproducible bit for bit.  The kernel sits beside the fill: it reads the resident batch and writes
-// arrays of its own.
+// its drawn offset by the banded dynamic program of fig_band.h against the EMITTED sequence (string + the batch's flank codes), the
+// best path is traced back, its insertions and deletions are moved as far left as they go, and per column the reads that ask for an
+// edit and the reads that span the column are counted.  Every output is reproducible bit for bit (fig_band.h).  The kernel sits
+// beside the fill: it reads the resident batch and writes arrays of its own.
 //
-// The cell update, the relaxation step of the deletion sweep, the end choice and the traceback with its normalisation are
-// __host__ __device__ functions; a plain C++ build compiles the same text.  The kernel is compiled in a translation unit of its own
-// (fig_indel_kernel.hip defines FIG_INDEL_KERNEL; fig_abi.hip sees the argument struct and fig_indel_launch only): with it in
-// fig_abi.hip's module the back end scheduled the unchanged fill kernels differently, at the same resource figures.
+// The traceback with its normalisation is a __host__ __device__ function; a plain C++ build compiles the same text.  The kernel is
+// compiled in a translation unit of its own (fig_indel_kernel.hip defines FIG_INDEL_KERNEL; fig_abi.hip sees the argument struct and
+// fig_indel_launch only): with it in fig_abi.hip's module the back end scheduled the unchanged fill kernels differently, at the same
+// resource figures.
 #ifndef FIG_INDEL_H
 #define FIG_INDEL_H
 #include <stdint.h>
-#include "fig_indel_host.h"
+#include "fig_band.h"
 #include "fig_placement.h"
-
-#define FIG_ID_NT (4 * FIG_RS_CHUNK)                 // threads of a workgroup; a work item is one chunk of reads
-#define FIG_ID_ROW 16                                // lanes of a read: its 15 diagonals and the -inf border above d = +W
-#define FIG_ID_GROUP (FIG_ID_NT / FIG_ID_ROW)        // reads in flight at a time
-#define FIG_ID_WIN ((FIG_RS_MAXL + 2 * FIG_INDEL_W + 1 + 3) & ~3)   // column codes a read's band can touch (+1: the border lane's read)
-#define FIG_ID_DIAG 0                                // back-pointers
-#define FIG_ID_INS 1
-#define FIG_ID_DEL 2
-
-// The substitution term of read base (s, k) on a column of code c
-template <typename DP>
-FIG_P_HD inline double fig_indel_term(int c, int s, int k, DP lm, DP le, DP lt) {
-    return c > 3 ? FIG_INDEL_LQ : c == s ? lm[k] : le[k] + lt[(c & 3) * 4 + s];
-}
-
-// H(i, d) before the deletion sweep, from H(i-1, d) and H(i-1, d+1) (-inf for d = +W): base_ok false = the read base is outside ACGT
-FIG_P_HD inline double fig_indel_cell(double h_diag, double h_up, bool base_ok, double t, double lI, int &bp) {
-    const double diag = base_ok ? h_diag + t : h_diag;
-    const double ins = h_up + lI;
-    bp = diag >= ins ? FIG_ID_DIAG : FIG_ID_INS;
-    return diag >= ins ? diag : ins;
-}
-
-// One relaxation of the deletion sweep: h = H(i, d), below = H(i, d-1).  True iff h rose.  The sequential sweep applies it once per
-// diagonal in ascending d; the kernel applies it to all diagonals at once until none rises: round t finishes the chains of t
-// deletions, each by the sweep's own additions in the sweep's own order, and max is exact, so the fixed point is the sweep's H bit
-// for bit and a cell ends above its first value iff the sweep gave it the DEL pointer (tests/indel_read_main.cpp holds the two
-// against each other).
-FIG_P_HD inline bool fig_indel_relax(double &h, double below, double lD) {
-    const double v = below + lD;
-    if (v > h) { h = v; return true; }
-    return false;
-}
-
-// The end of the path: the greatest of H[q] = H(len, q - W), ties to the first diagonal of fig_indel_end_order
-template <typename HP>
-FIG_P_HD inline double fig_indel_end(HP H, int &d_end) {
-    double best = H[FIG_INDEL_W];
-    d_end = 0;
-    for (int t = 1; t < FIG_INDEL_ND; t++) {
-        const int d = fig_indel_end_order(t);
-        const double v = H[d + FIG_INDEL_W];
-        if (v > best) { best = v; d_end = d; }
-    }
-    return best;
-}
 
 // The traceback from (len, d_end) to row 0 and the left-normalised events of the path.  bp(i, d): the back-pointer of cell (i, d),
 // 1 <= i <= len; S[x - o + W]: the code of column x; w: the read's words (fig_rs_base).  sink.ins(x): an INS run whose next column is
@@ -100,21 +52,8 @@ FIG_P_HD inline void fig_indel_traceback(BP bp, SP S, WP w, int len, int rev, in
 }
 
 #ifdef __HIPCC__
-// What the kernel reads (all device memory; every array is read through an address-space-1 view) and the arrays it writes.
-struct FigIndelArgs {
-    const FigDevGap *gaps;           // the resident batch's descriptors: nU, uBase, flankOff
-    const int32_t *u_len, *u_aux;
-    const int64_t *u_woff;
-    const uint32_t *packed;
-    const uint8_t *flank;
-    const int32_t *draw_pos;         // [n_ureads] drawn offset, INT32_MIN = not drawn
-    const int32_t *items;            // [gridDim.x * 2] {gap, first read of the chunk within the gap}
-    const int32_t *ncol;             // [n_gaps] bases of the gap's string
-    const int64_t *str_off;          // [n_gaps + 1] the caller's (compacted) string offsets
-    const char *str;                 // the caller's strings
-    const double *tabs;              // lm[L] | le[L] | lt[16]
-    const double *tabs_id;           // lI[L] | lD[L]
-    int32_t L;
+// What the kernel reads (FigBandIn; items: {gap, first read of the chunk within the gap}) and the arrays it writes.
+struct FigIndelArgs : FigBandIn {
     double *ll_flat, *ll_gapped;     // [n_ureads], written for aligned reads only
     int32_t *n_ins, *n_del, *d_end, *d_start;
     int32_t *del_reads, *ins_reads, *cover;   // [str_off[n_gaps]], zeroed by the caller, added to atomically
@@ -136,12 +75,9 @@ struct FigIndelSink {
     __device__ void del(int x, int m) { for (int c = x; c < x + m; c++) if (c >= 0 && c < n) add(del_reads + c); }
 };
 
-// One workgroup per (gap that is on, chunk of 64 of its reads), the chunk staged in LDS once; 16 reads at a time.  A read's band
-// lives in one 16-lane row of a wave: lane q < 15 holds H(i, q - 7) in a register and lane 15 the -inf above d = +7, four reads per
-// wave.  A row of the band is one step of the wave: the INS neighbour H(i-1, d+1) comes from the lane above and the DEL neighbour
-// H(i, d-1) from the lane below by row-wise shuffles, and the deletion sweep repeats fig_indel_relax on all diagonals until a ballot
-// says no lane rose.  The back-pointers of a (read, row) are two ballots' 16-bit slices in one LDS dword.  One lane per read takes
-// the end, walks back and adds its events to the planes; the 16 lanes of the row add the cover.
+// One workgroup per (gap that is on, chunk of 64 of its reads), the chunk staged in LDS once; 16 reads at a time, a read's band in
+// one 16-lane row of a wave (fig_band_forward, with back-pointers and the flat score).  One lane per read takes the end, walks back
+// and adds its events to the planes; the 16 lanes of the row add the cover.
 __global__ void __launch_bounds__(FIG_ID_NT) fig_indel_kernel(FigIndelArgs A) {
     __shared__ double s_tab[FIG_RS_TAB];
     __shared__ double s_id[2 * FIG_RS_MAXL];                     // lI at 0, lD at FIG_RS_MAXL
@@ -150,7 +86,7 @@ __global__ void __launch_bounds__(FIG_ID_NT) fig_indel_kernel(FigIndelArgs A) {
     __shared__ uint32_t s_bp[FIG_ID_GROUP][FIG_RS_MAXL];         // row i at [i - 1]: bit q = INS, bit 16 + q = DEL of diagonal q - 7
     __shared__ uint8_t s_S[FIG_ID_GROUP][FIG_ID_WIN];            // [x - (o - 7)]
     __shared__ double s_H[FIG_ID_GROUP][FIG_ID_ROW], s_flat[FIG_ID_GROUP];
-    const int tid = (int)threadIdx.x, lane = tid & 63, rr = tid / FIG_ID_ROW, q = tid & (FIG_ID_ROW - 1);
+    const int tid = (int)threadIdx.x, rr = tid / FIG_ID_ROW, q = tid & (FIG_ID_ROW - 1);
     const int g = ((fig_rs_gi32p)A.items)[2 * blockIdx.x], c0 = ((fig_rs_gi32p)A.items)[2 * blockIdx.x + 1];
     fig_rs_ggapp gp = (fig_rs_ggapp)A.gaps + g;
     const int n = ((fig_rs_gi32p)A.ncol)[g];
@@ -161,7 +97,7 @@ __global__ void __launch_bounds__(FIG_ID_NT) fig_indel_kernel(FigIndelArgs A) {
     const long long soff = ((fig_rs_gi64p)A.str_off)[g];
     fig_rs_gcp str = (fig_rs_gcp)A.str + soff;
     fig_rs_stage_tables(s_tab, A.tabs, L, tid, FIG_ID_NT);
-    for (int i = tid; i < 2 * L; i += FIG_ID_NT) s_id[i < L ? i : FIG_RS_MAXL + (i - L)] = ((fig_rs_gcdp)A.tabs_id)[i];
+    fig_band_stage_id(s_id, A.tabs_id, L, tid, FIG_ID_NT);
     fig_rs_ldp lm = (fig_rs_ldp)&s_tab[0], le = (fig_rs_ldp)&s_tab[L], lt = (fig_rs_ldp)&s_tab[2 * FIG_RS_MAXL];
     fig_rs_ldp lI = (fig_rs_ldp)&s_id[0], lD = (fig_rs_ldp)&s_id[FIG_RS_MAXL];
     const double ninf = -__builtin_inf();
@@ -177,36 +113,10 @@ __global__ void __launch_bounds__(FIG_ID_NT) fig_indel_kernel(FigIndelArgs A) {
         const int o = h4.x, len = h4.y, rev = h4.z;
         const bool al = h4.w != 0;
         fig_rs_lu32p w = (fig_rs_lu32p)&s_w[r < nc ? r : 0][0];
-        if (al) for (int i = q; i < len + 2 * FIG_INDEL_W; i += FIG_ID_ROW) s_S[rr][i] = (uint8_t)fig_placement_column(o - FIG_INDEL_W + i, n, fl, str);
+        if (al) fig_band_window(&s_S[rr][0], o, len, q, [&](int x) { return fig_placement_column(x, n, fl, str); });
         __syncthreads();
-        int rows = al ? len : 0;                                 // the wave walks to its longest read
-        rows = max(rows, __shfl_xor(rows, 16, 64)); rows = max(rows, __shfl_xor(rows, 32, 64));
-        double h = q < FIG_INDEL_ND ? 0.0 : ninf, flat = 0.0;
-        for (int i = 1; i <= rows; i++) {
-            const bool active = al && i <= len;
-            const double up = __shfl_down(h, 1, FIG_ID_ROW);     // H(i-1, d+1); lane 14 gets the border's -inf, lane 15 itself
-            double hn = h, ld = ninf;
-            int bp = FIG_ID_DIAG;
-            if (active) {
-                int s, k;
-                const bool ok = fig_rs_base(w, len, rev, i - 1, s, k);
-                const double t = fig_indel_term((int)s_S[rr][i - 1 + q], s, k, lm, le, lt);
-                hn = fig_indel_cell(h, up, ok, t, lI[k], bp);
-                if (ok) flat = flat + t;                         // lane 7's is the read's: d = 0
-                ld = lD[k];
-            }
-            const bool sweep = active && i < len && q >= 1 && q < FIG_INDEL_ND;
-            bool rose;
-            do {
-                const double below = __shfl_up(hn, 1, FIG_ID_ROW);
-                rose = sweep && fig_indel_relax(hn, below, ld);
-                if (rose) bp = FIG_ID_DEL;
-            } while (__ballot(rose));
-            const unsigned long long b_ins = __ballot(bp == FIG_ID_INS), b_del = __ballot(bp == FIG_ID_DEL);
-            if (active && q == 0) s_bp[rr][i - 1] = (uint32_t)((b_ins >> (lane & 48)) & 0xffffu) | ((uint32_t)((b_del >> (lane & 48)) & 0xffffu) << 16);
-            h = hn;
-        }
-        s_H[rr][q] = h;
+        double flat;
+        s_H[rr][q] = fig_band_forward<true, true>((fig_rs_lu8p)&s_S[rr][0], w, al, len, rev, q, lm, le, lt, lI, lD, &s_bp[rr][0], &flat);
         if (q == FIG_INDEL_W) s_flat[rr] = flat;
         __syncthreads();
         int lo = 0, hi = -1;
@@ -216,10 +126,7 @@ __global__ void __launch_bounds__(FIG_ID_NT) fig_indel_kernel(FigIndelArgs A) {
             if (best > ninf) {
                 FigIndelSink sink = { (fig_id_gcnt)A.del_reads + soff, (fig_id_gcnt)A.ins_reads + soff, (fig_id_gcnt)A.ins_end + g, n };
                 const uint32_t *row = &s_bp[rr][0];
-                auto bpf = [row](int i, int d) {
-                    const uint32_t v = row[i - 1] >> (d + FIG_INDEL_W);
-                    return (v & 1u) ? FIG_ID_INS : (v & 0x10000u) ? FIG_ID_DEL : FIG_ID_DIAG;
-                };
+                auto bpf = [row](int i, int d) { return fig_band_bp(row, i, d); };
                 fig_indel_traceback(bpf, (fig_rs_lu8p)&s_S[rr][0], w, len, rev, o, d_end, sink, d_start, n_ins, n_del);
                 lo = max(o + d_start, 0); hi = min(o + len - 1 + d_end, n - 1);
             } else d_end = 0;

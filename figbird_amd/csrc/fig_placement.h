@@ -5,7 +5,9 @@
 // addition each, and the rest is comparisons: ll_drawn, ll_other, off_other and n_valid are reproducible bit for bit.  The kernel
 // sits beside the fill: it reads the resident batch and writes five arrays of its own.
 //
-// The arithmetic of one (read, placement) pair is one __host__ __device__ function; a plain C++ build compiles the same text.
+// The arithmetic of one (read, placement) pair is one __host__ __device__ function; a plain C++ build compiles the same text.  The
+// kernel is defined where FIG_PLACEMENT_KERNEL is (fig_abi.hip, whose module owns it); the other kernels' units take the column and
+// score functions and the wave reductions without it.
 #ifndef FIG_PLACEMENT_H
 #define FIG_PLACEMENT_H
 #include <stdint.h>
@@ -70,6 +72,7 @@ __device__ inline double fig_p_wave_sum(double v) {
     return v;
 }
 
+#ifdef FIG_PLACEMENT_KERNEL
 // One workgroup per (gap that is on, chunk of 64 of its reads).  The chunk's reads are staged in LDS once.  The offsets
 // -(200-1) .. n-1 pass in tiles of 256: a lane owns offset o = x0 + tid, the tile's columns x0 .. x0 + 256 + 198 are staged as
 // codes, and the waves walk the staged reads -- length, orientation, anchor, drawn offset and every read base are wave-uniform, a
@@ -173,5 +176,6 @@ __global__ void __launch_bounds__(FIG_P_NT) fig_placement_kernel(FigPlaceArgs A)
         __syncthreads();
     }
 }
+#endif
 #endif
 #endif

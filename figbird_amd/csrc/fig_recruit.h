@@ -1,19 +1,20 @@
 // fig_recruit.h -- the kernel of the recruiting pass (fig_batch_recruit; include/figbird_hip.h: fig_read_recruit):
 // every UNDRAWN read of a gap is scored on all its placements against the emitted sequence (fig_placement.h's tile loop and
-// fig_placement_score), the best valid placement seeds the banded dynamic program of fig_indel.h, and the best valid placement
+// fig_placement_score), the best valid placement seeds the banded dynamic program of fig_band.h, and the best valid placement
 // outside the band around the seed is reported beside it.  A score only ADDS entries of the log10 tables the host built, one IEEE
 // double addition each, and the rest is comparisons: every output is reproducible bit for bit.  There is no exp10, no traceback and
 // no atomic.  The kernel sits beside the fill: it reads the resident batch and writes nine arrays of its own.
 //
 // The score of one (read, placement), the band's cell and the order of two (score, offset) pairs are __host__ __device__ functions
-// (fig_placement.h, fig_indel.h, fig_recruit_host.h); a plain C++ build compiles the same text (tests/recruit_read_main.cpp).  Like
+// (fig_placement.h, fig_band.h, fig_recruit_host.h); a plain C++ build compiles the same text (tests/recruit_read_main.cpp).  Like
 // fig_indel_kernel the kernel is compiled in a translation unit of its own (fig_recruit_kernel.hip defines FIG_RECRUIT_KERNEL;
 // fig_abi.hip sees the argument struct and fig_recruit_launch only).
 #ifndef FIG_RECRUIT_H
 #define FIG_RECRUIT_H
 #include <stdint.h>
 #include "fig_recruit_host.h"
-#include "fig_indel.h"
+#include "fig_band.h"
+#include "fig_placement.h"
 
 #define FIG_RC_NT FIG_P_NT                           // threads of a workgroup = offsets of a tile; a work item is one chunk of reads
 #define FIG_RC_WAVES (FIG_RC_NT / 64)
@@ -25,7 +26,9 @@ FIG_P_HD inline void fig_recruit_wave_slot(bool any, double wmax, int first, dou
 }
 
 #ifdef __HIPCC__
-// What the kernel reads (all device memory; every array is read through an address-space-1 view) and the arrays it writes.
+// What the kernel reads (all device memory; every array is read through an address-space-1 view) and the arrays it writes.  The
+// members of FigBandIn in the order this kernel has always had them, u_pos and li among them: with FigBandIn as the struct's base
+// the kernel measured 1.4 - 2.4 % slower (profiles/band/README.md); fig_batch_recruit copies them out of a FigBandIn.
 struct FigRecruitArgs {
     const FigDevGap *gaps;           // the resident batch's descriptors: nU, uBase, gapStart, G0, flankOff
     const int32_t *u_len, *u_aux, *u_pos;
@@ -59,10 +62,8 @@ hipError_t fig_recruit_launch(const FigRecruitArgs &A, unsigned items, hipStream
 // four waves by one thread per read.  Pass 1 does the same over the valid offsets outside off_seed +- 7.  A read that is not seeded
 // drops out after pass 0.
 //
-// Then the band, exactly as fig_polish_kernel runs it: 16 reads at a time, a read's band in one 16-lane row of a wave, lane q < 15
-// holds H(i, q - 7), lane 15 the -inf above d = +7, the INS neighbour comes from the lane above and the DEL neighbour from the lane
-// below by row-wise shuffles, and the deletion sweep repeats fig_indel_relax until a ballot says no lane rose.  Forward only; one
-// lane per read takes the end and writes the read's values.
+// Then the band: 16 reads at a time, a read's band in one 16-lane row of a wave (fig_band_forward, forward only, with the flat
+// score); one lane per read takes the end and writes the read's values.
 __global__ void __launch_bounds__(FIG_RC_NT) fig_recruit_kernel(FigRecruitArgs A) {
     __shared__ double s_tab[FIG_RS_TAB];
     __shared__ double s_id[2 * FIG_RS_MAXL];                     // lI at 0, lD at FIG_RS_MAXL
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(FIG_RC_NT) fig_recruit_kernel(FigRecruitArgs A
     fig_rs_gcp str = (fig_rs_gcp)A.str + ((fig_rs_gi64p)A.str_off)[g];
     fig_rs_gcdp li = (fig_rs_gcdp)A.li;
     fig_rs_stage_tables(s_tab, A.tabs, L, tid, FIG_RC_NT);
-    for (int i = tid; i < 2 * L; i += FIG_RC_NT) s_id[i < L ? i : FIG_RS_MAXL + (i - L)] = ((fig_rs_gcdp)A.tabs_id)[i];
+    fig_band_stage_id(s_id, A.tabs_id, L, tid, FIG_RC_NT);
     fig_rs_ldp lm = (fig_rs_ldp)&s_tab[0], le = (fig_rs_ldp)&s_tab[L], lt = (fig_rs_ldp)&s_tab[2 * FIG_RS_MAXL];
     fig_rs_ldp lI = (fig_rs_ldp)&s_id[0], lD = (fig_rs_ldp)&s_id[FIG_RS_MAXL];
     const double ninf = -__builtin_inf();
@@ -153,32 +154,10 @@ __global__ void __launch_bounds__(FIG_RC_NT) fig_recruit_kernel(FigRecruitArgs A
         const int o = h4.x, len = h4.y, rev = h4.z;
         const bool al = len != 0;
         fig_rs_lu32p w = (fig_rs_lu32p)&s_w[r < nc ? r : 0][0];
-        if (al) for (int i = q; i <= len + 2 * FIG_INDEL_W; i += FIG_ID_ROW) s_B[rr][i] = (uint8_t)fig_placement_column(o - FIG_INDEL_W + i, n, fl, str);
+        if (al) fig_band_window(&s_B[rr][0], o, len, q, [&](int x) { return fig_placement_column(x, n, fl, str); });
         __syncthreads();
-        int rows = al ? len : 0;                                 // the wave walks to its longest read
-        rows = max(rows, __shfl_xor(rows, 16, 64)); rows = max(rows, __shfl_xor(rows, 32, 64));
-        double h = q < FIG_INDEL_ND ? 0.0 : ninf, flat = 0.0;
-        for (int i = 1; i <= rows; i++) {
-            const bool active = al && i <= len;
-            const double up = __shfl_down(h, 1, FIG_ID_ROW);     // H(i-1, d+1); lane 14 gets the border's -inf, lane 15 itself
-            double hn = h, ld = ninf;
-            if (active) {
-                int s, k, bp;
-                const bool ok = fig_rs_base(w, len, rev, i - 1, s, k);
-                const double t = fig_indel_term((int)s_B[rr][i - 1 + q], s, k, lm, le, lt);
-                hn = fig_indel_cell(h, up, ok, t, lI[k], bp);
-                if (ok) flat = flat + t;                         // lane 7's is the read's: d = 0
-                ld = lD[k];
-            }
-            const bool sweep = active && i < len && q >= 1 && q < FIG_INDEL_ND;
-            bool rose;
-            do {
-                const double below = __shfl_up(hn, 1, FIG_ID_ROW);
-                rose = sweep && fig_indel_relax(hn, below, ld);
-            } while (__ballot(rose));
-            h = hn;
-        }
-        s_H[rr][q] = h;
+        double flat;
+        s_H[rr][q] = fig_band_forward<false, true>((fig_rs_lu8p)&s_B[rr][0], w, al, len, rev, q, lm, le, lt, lI, lD, nullptr, &flat);
         if (q == FIG_INDEL_W) s_flat[rr] = flat;
         __syncthreads();
         if (al && q == 0) {

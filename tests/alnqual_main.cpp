@@ -1,7 +1,7 @@
-// The pieces the two kernels of fig_alnqual.h run -- the band of fig_indel.h, fig_alnqual_walk, fig_alnqual_flat, fig_alnqual_span,
-// the nibble map and fig_alnqual_add_read, compiled as plain C++ -- over a case file, in the kernels' form (16 "lanes" per read with
-// the deletion sweep as repeated relaxation and back-pointers as two 16-bit masks per row; a map of FIG_ALNQ_MAPB bytes per read;
-// per column a walk over the reads in chunks of 64, in order) and, beside it, a sequential restatement of the definition in
+// The pieces the two kernels of fig_alnqual.h run -- the band of fig_band.h, fig_alnqual_walk, fig_alnqual_flat, fig_alnqual_span,
+// the nibble map and fig_alnqual_add_read, compiled as plain C++ -- over a case file, in the kernels' form (band_form.h's 16
+// "lanes" per read with the deletion sweep as repeated relaxation and back-pointers as two 16-bit masks per row; a map of
+// FIG_ALNQ_MAPB bytes per read; per column a walk over the reads in chunks of 64, in order) and, beside it, a sequential restatement of the definition in
 // figbird_hip.h written out here (a full matrix, the sweep in ascending d, the steps listed from the end and replayed forwards into
 // the planes read by read).  The two must agree in every map entry, every per-read value and every plane, doubles bit for bit: exit 4
 // with a message otherwise.  Built with AddressSanitizer and UBSan by tests/test_alnqual.py and run directly.
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../figbird_amd/csrc/fig_alnqual.h"
+#include "band_form.h"
 
 static double rd(std::istream &in) { std::string t; in >> t; return strtod(t.c_str(), nullptr); }
 static uint64_t bits(double v) { uint64_t u; memcpy(&u, &v, 8); return u; }
@@ -37,41 +38,14 @@ struct Planes { std::vector<double> ll; std::vector<int> depth, agree, skip; };
 static Path lane_form(const Read &R, const Tabs &T) {
     const int len = R.len;
     double h[16];
-    for (int q = 0; q < 16; q++) h[q] = q < ND ? 0.0 : NINF;
     std::vector<uint32_t> bpw((size_t)len, 0u);
-    for (int i = 1; i <= len; i++) {
-        double hn[16], ld = NINF;
-        int bp[16];
-        for (int q = 0; q < 16; q++) {
-            const double up = q < 15 ? h[q + 1] : h[q];                      // __shfl_down(h, 1, 16)
-            int s, k;
-            const bool ok = fig_rs_base(R.w.data(), len, R.rev, i - 1, s, k);
-            const double t = fig_indel_term((int)R.S[(size_t)(i - 1 + q)], s, k, T.lm.data(), T.le.data(), T.lt.data());
-            hn[q] = fig_indel_cell(h[q], up, ok, t, T.lI[(size_t)k], bp[q]);
-            ld = T.lD[(size_t)k];
-        }
-        bool any;
-        do {
-            any = false;
-            double prev[16];
-            memcpy(prev, hn, sizeof(prev));
-            for (int q = 0; q < 16; q++) {
-                const double below = q > 0 ? prev[q - 1] : prev[q];          // __shfl_up(hn, 1, 16)
-                const bool rose = i < len && q >= 1 && q < ND && fig_indel_relax(hn[q], below, ld);
-                if (rose) { bp[q] = FIG_ID_DEL; any = true; }
-            }
-        } while (any);
-        uint32_t m = 0;
-        for (int q = 0; q < 16; q++) m |= (bp[q] == FIG_ID_INS ? 1u << q : 0u) | (bp[q] == FIG_ID_DEL ? 1u << (16 + q) : 0u);
-        bpw[(size_t)(i - 1)] = m;
-        memcpy(h, hn, sizeof(h));
-    }
+    band_form(R.S.data(), R.w.data(), len, R.rev, T.lm.data(), T.le.data(), T.lt.data(), T.lI.data(), T.lD.data(), h, bpw.data(), nullptr, nullptr);
     Path p;
     p.map.assign((size_t)FIG_ALNQ_MAPB, 0xff);
     p.gapped = fig_indel_end(h, p.d_end);
     if (p.gapped > NINF) {
         const uint32_t *row = bpw.data();
-        auto bpf = [row](int i, int d) { const uint32_t v = row[i - 1] >> (d + W); return (v & 1u) ? FIG_ID_INS : (v & 0x10000u) ? FIG_ID_DEL : FIG_ID_DIAG; };
+        auto bpf = [row](int i, int d) { return fig_band_bp(row, i, d); };
         fig_alnqual_walk(bpf, p.map.data(), len, p.d_end, p.d_start, p.n_ins, p.n_del);
     } else fig_alnqual_flat(p.map.data(), len, p.d_start, p.d_end, p.n_ins, p.n_del);
     fig_alnqual_span(R.o, len, p.d_start, p.d_end, p.lo, p.hi);

@@ -1,6 +1,6 @@
 // The pieces fig_indel_kernel runs per read -- fig_indel_term, fig_indel_cell, fig_indel_relax, fig_indel_end, fig_indel_traceback,
-// compiled as plain C++ -- over a case file, in the kernel's form (16 "lanes" per read: the update from the lane above, the deletion
-// sweep as repeated relaxation of all diagonals until none rises, back-pointers as two 16-bit masks per row) and, beside it, a
+// compiled as plain C++ -- over a case file, in the kernel's form (band_form.h's 16 "lanes" per read: the update from the lane
+// above, the deletion sweep as repeated relaxation of all diagonals until none rises, back-pointers as two 16-bit masks per row) and, beside it, a
 // sequential restatement of the definition in figbird_hip.h written out here (a full matrix, the sweep in ascending d, a traceback
 // that lists steps first and normalises afterwards).  The two must agree bit for bit in every cell, pointer and output: exit 4
 // with a message otherwise.  Built with AddressSanitizer and UBSan by tests/test_indel_evidence.py and run directly.
@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../figbird_amd/csrc/fig_indel.h"
+#include "band_form.h"
 
 static double rd(std::istream &in) { std::string t; in >> t; return strtod(t.c_str(), nullptr); }
 static uint64_t bits(double v) { uint64_t u; memcpy(&u, &v, 8); return u; }
@@ -41,48 +42,17 @@ struct Tabs { std::vector<double> lm, le, lt, lI, lD; };
 // ---- the kernel's form
 static Out lane_form(const Read &R, const Tabs &T, std::vector<double> &Hall, std::vector<uint32_t> &bpw) {
     const int len = R.len;
-    double h[16];
-    for (int q = 0; q < 16; q++) h[q] = q < ND ? 0.0 : NINF;
-    double flat = 0.0;
+    double h[16], flat;
     bpw.assign((size_t)len, 0u);
     Hall.assign((size_t)(len + 1) * ND, 0.0);
-    for (int i = 1; i <= len; i++) {
-        double hn[16], ld = NINF;
-        int bp[16];
-        for (int q = 0; q < 16; q++) {
-            const double up = q < 15 ? h[q + 1] : h[q];                      // __shfl_down(h, 1, 16)
-            int s, k;
-            const bool ok = fig_rs_base(R.w.data(), len, R.rev, i - 1, s, k);
-            const double t = fig_indel_term((int)R.S[(size_t)(i - 1 + q)], s, k, T.lm.data(), T.le.data(), T.lt.data());
-            hn[q] = fig_indel_cell(h[q], up, ok, t, T.lI[(size_t)k], bp[q]);
-            if (q == W && ok) flat = flat + t;
-            ld = T.lD[(size_t)k];
-        }
-        bool any;
-        do {
-            any = false;
-            double prev[16];
-            memcpy(prev, hn, sizeof(prev));
-            for (int q = 0; q < 16; q++) {
-                const double below = q > 0 ? prev[q - 1] : prev[q];          // __shfl_up(hn, 1, 16)
-                const bool rose = i < len && q >= 1 && q < ND && fig_indel_relax(hn[q], below, ld);
-                if (rose) { bp[q] = FIG_ID_DEL; any = true; }
-            }
-        } while (any);
-        uint32_t m = 0;
-        for (int q = 0; q < 16; q++) m |= (bp[q] == FIG_ID_INS ? 1u << q : 0u) | (bp[q] == FIG_ID_DEL ? 1u << (16 + q) : 0u);
-        bpw[(size_t)(i - 1)] = m;
-        memcpy(h, hn, sizeof(h));
-        if (h[15] != NINF) { fprintf(stderr, "the border lane left -inf\n"); exit(4); }
-        for (int q = 0; q < ND; q++) Hall[(size_t)i * ND + q] = h[q];
-    }
+    band_form(R.S.data(), R.w.data(), len, R.rev, T.lm.data(), T.le.data(), T.lt.data(), T.lI.data(), T.lD.data(), h, bpw.data(), &flat, Hall.data());
     Out o; o.flat = flat;
     o.gapped = fig_indel_end(h, o.d_end);
     o.n_ins = o.n_del = 0; o.d_start = 0;
     if (o.gapped > NINF) {
         Events ev;
         const uint32_t *row = bpw.data();
-        auto bpf = [row](int i, int d) { const uint32_t v = row[i - 1] >> (d + W); return (v & 1u) ? FIG_ID_INS : (v & 0x10000u) ? FIG_ID_DEL : FIG_ID_DIAG; };
+        auto bpf = [row](int i, int d) { return fig_band_bp(row, i, d); };
         fig_indel_traceback(bpf, R.S.data(), R.w.data(), len, R.rev, R.o, o.d_end, ev, o.d_start, o.n_ins, o.n_del);
         o.ev = ev.text;
     } else o.d_end = 0;
@@ -192,7 +162,7 @@ int main(int argc, char **argv) {
         // every cell and pointer of the repeated-relaxation form against the sequential sweep, bit for bit
         for (int i = 1; i <= len; i++)
             for (int q = 0; q < ND; q++) {
-                const uint32_t v = bpw[(size_t)(i - 1)] >> q;
+                const uint32_t v = bpw[(size_t)(i - 1)] >> q;                // (this check's own decode, not fig_band_bp)
                 const int p = (v & 1u) ? FIG_ID_INS : (v & 0x10000u) ? FIG_ID_DEL : FIG_ID_DIAG;
                 if (bits(Hk[(size_t)i * ND + q]) != bits(Hs[(size_t)i * ND + q]) || p != Ps[(size_t)i * ND + q]) {
                     fprintf(stderr, "read %d cell (%d, %d): kernel form %a / %d, sequential %a / %d\n", r, i, q - W, Hk[(size_t)i * ND + q], p, Hs[(size_t)i * ND + q], Ps[(size_t)i * ND + q]);

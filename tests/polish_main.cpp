@@ -1,6 +1,6 @@
 // The pieces fig_polish_kernel runs per (candidate, read) -- fig_polish_counted, fig_polish_shift, fig_polish_column and the band of
-// fig_indel.h, compiled as plain C++ -- over a case file, in the kernel's form (16 "lanes" per read, the column codes of the EDITED
-// sequence taken from the unedited string through fig_polish_column, the deletion sweep as repeated relaxation, forward only) and,
+// fig_band.h, compiled as plain C++ -- over a case file, in the kernel's form (band_form.h's 16 "lanes" per read, the column codes of
+// the EDITED sequence taken from the unedited string through fig_polish_column, the deletion sweep as repeated relaxation, forward only) and,
 // beside it, a sequential restatement written out here: the edited string is built, its columns are read with the flanks moved to
 // its ends, and ll_c is the greatest cell of the last row of a full matrix filled by the definition in figbird_hip.h.  The two must
 // agree bit for bit: exit 4 with a message otherwise.  Then the bookkeeping of the edit planes (fig_polish_host.h) runs a script of
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../figbird_amd/csrc/fig_polish.h"
+#include "band_form.h"
 
 static double rd(std::istream &in) { std::string t; in >> t; return strtod(t.c_str(), nullptr); }
 static uint64_t bits(double v) { uint64_t u; memcpy(&u, &v, 8); return u; }
@@ -37,30 +38,7 @@ static double lane_form(const Read &R, const Tabs &T, int n, const uint8_t *fl, 
     std::vector<uint8_t> S((size_t)len + 2 * W + 1);
     for (int i = 0; i <= len + 2 * W; i++) S[(size_t)i] = (uint8_t)fig_polish_column(oc - W + i, n, fl, str, kind, x, b);
     double h[16];
-    for (int q = 0; q < 16; q++) h[q] = q < ND ? 0.0 : NINF;
-    for (int i = 1; i <= len; i++) {
-        double hn[16], ld = NINF;
-        for (int q = 0; q < 16; q++) {
-            const double up = q < 15 ? h[q + 1] : h[q];                      // __shfl_down(h, 1, 16)
-            int s, k, bp;
-            const bool ok = fig_rs_base(R.w.data(), len, R.rev, i - 1, s, k);
-            const double t = fig_indel_term((int)S[(size_t)(i - 1 + q)], s, k, T.lm.data(), T.le.data(), T.lt.data());
-            hn[q] = fig_indel_cell(h[q], up, ok, t, T.lI[(size_t)k], bp);
-            ld = T.lD[(size_t)k];
-        }
-        bool any;
-        do {
-            any = false;
-            double prev[16];
-            memcpy(prev, hn, sizeof(prev));
-            for (int q = 0; q < 16; q++) {
-                const double below = q > 0 ? prev[q - 1] : prev[q];          // __shfl_up(hn, 1, 16)
-                if (i < len && q >= 1 && q < ND && fig_indel_relax(hn[q], below, ld)) any = true;
-            }
-        } while (any);
-        memcpy(h, hn, sizeof(h));
-        if (h[15] != NINF) { fprintf(stderr, "the border lane left -inf\n"); exit(4); }
-    }
+    band_form(S.data(), R.w.data(), len, R.rev, T.lm.data(), T.le.data(), T.lt.data(), T.lI.data(), T.lD.data(), h, nullptr, nullptr, nullptr);
     int d_end;
     return fig_indel_end(h, d_end);
 }

@@ -1,9 +1,9 @@
 // The pieces fig_recruit_kernel runs per candidate read -- fig_placement_column, fig_placement_isz, fig_placement_valid,
-// fig_placement_score, the slot order of fig_recruit_host.h and the band of fig_indel.h, compiled as plain C++ -- over a case file, in
+// fig_placement_score, the slot order of fig_recruit_host.h and the band of fig_band.h, compiled as plain C++ -- over a case file, in
 // the kernel's form (tiles of 256 offsets from -199, four "waves" of 64 lanes with a slot each, the butterfly maximum and the first
-// lane of a ballot, two passes, then 16 "lanes" per read with the deletion sweep as repeated relaxation) and, beside it, a sequential
-// restatement written out here: one loop over the offsets in ascending order that keeps the first strict maximum, the same loop over
-// the offsets outside the window, and a full matrix filled by the definition in figbird_hip.h.  The two must agree in every output
+// lane of a ballot, two passes, then band_form.h's 16 "lanes" per read with the deletion sweep as repeated relaxation) and, beside
+// it, a sequential restatement written out here: one loop over the offsets in ascending order that keeps the first strict maximum,
+// the same loop over the offsets outside the window, and a full matrix filled by the definition in figbird_hip.h.  The two must agree in every output
 // bit for bit: exit 4 with a message otherwise.  Built with AddressSanitizer and UBSan by tests/test_recruit.py and run directly.
 //
 // case file: L | lm[L] | le[L] | lt[16] | lI[L] | lD[L] | MI | li[MI] | Tmin Tmax | gaps, then per gap `n gap_start G0 reads` | 416
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../figbird_amd/csrc/fig_recruit.h"
+#include "band_form.h"
 
 static double rd(std::istream &in) { std::string t; in >> t; return strtod(t.c_str(), nullptr); }
 static uint64_t bits(double v) { uint64_t u; memcpy(&u, &v, 8); return u; }
@@ -83,32 +84,8 @@ static Out kernel_form(const Read &R, const Tabs &T, int n, long long gap_start,
     }
     std::vector<uint8_t> B((size_t)len + 2 * W + 1);
     for (int i = 0; i <= len + 2 * W; i++) B[(size_t)i] = (uint8_t)fig_placement_column(seed - W + i, n, fl, str);
-    double h[16], flat = 0.0;
-    for (int q = 0; q < 16; q++) h[q] = q < ND ? 0.0 : NINF;
-    for (int i = 1; i <= len; i++) {
-        double hn[16], ld = NINF;
-        for (int q = 0; q < 16; q++) {
-            const double up = q < 15 ? h[q + 1] : h[q];                      // __shfl_down(h, 1, 16)
-            int s, k, bp;
-            const bool ok = fig_rs_base(R.w.data(), len, R.rev, i - 1, s, k);
-            const double t = fig_indel_term((int)B[(size_t)(i - 1 + q)], s, k, T.lm.data(), T.le.data(), T.lt.data());
-            hn[q] = fig_indel_cell(h[q], up, ok, t, T.lI[(size_t)k], bp);
-            if (ok && q == W) flat = flat + t;
-            ld = T.lD[(size_t)k];
-        }
-        bool any;
-        do {
-            any = false;
-            double prev[16];
-            memcpy(prev, hn, sizeof(prev));
-            for (int q = 0; q < 16; q++) {
-                const double below = q > 0 ? prev[q - 1] : prev[q];          // __shfl_up(hn, 1, 16)
-                if (i < len && q >= 1 && q < ND && fig_indel_relax(hn[q], below, ld)) any = true;
-            }
-        } while (any);
-        memcpy(h, hn, sizeof(h));
-        if (h[15] != NINF) { fprintf(stderr, "the border lane left -inf\n"); exit(4); }
-    }
+    double h[16], flat;
+    band_form(B.data(), R.w.data(), len, R.rev, T.lm.data(), T.le.data(), T.lt.data(), T.lI.data(), T.lD.data(), h, nullptr, &flat, nullptr);
     int d_end;
     o.ll_gapped = fig_indel_end(h, d_end);
     o.d_end = o.ll_gapped > NINF ? d_end : 0;

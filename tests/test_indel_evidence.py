@@ -585,8 +585,8 @@ def case_lines(H, Wt, tabs):
 
 
 def test_kernel_pieces_on_the_cpu(planted, edges, tmp_path):
-    """The __host__ __device__ pieces of fig_indel.h compiled as plain C++ into a program of its own with AddressSanitizer and UBSan
-    (tests/indel_read_main.cpp; run directly), over the aligned reads of the planted, the edge and the band case: inside the program
+    """The __host__ __device__ pieces of fig_indel.h and fig_band.h (the band in tests/band_form.h's form) compiled as plain C++ into a
+    program of its own with AddressSanitizer and UBSan (tests/indel_read_main.cpp; run directly), over the aligned reads of the planted, the edge and the band case: inside the program
     the kernel's form (lanes, repeated relaxation of the deletion sweep, packed pointers) equals a sequential restatement in every
     cell and pointer bit for bit; its output equals the numpy restatement, events included."""
     exe = str(tmp_path / "indel_read")

@@ -532,8 +532,8 @@ def _program_case(H, tabs):
 
 
 def test_kernel_pieces_on_the_cpu(withheld, edges, tmp_path):
-    """The __host__ __device__ pieces of fig_recruit.h, fig_recruit_host.h, fig_placement.h and fig_indel.h compiled as plain C++ into a
-    program of its own with AddressSanitizer and UBSan (tests/recruit_read_main.cpp; run directly), over the withheld, the edge, the
+    """The __host__ __device__ pieces of fig_recruit.h, fig_recruit_host.h, fig_placement.h and fig_band.h (the band in
+    tests/band_form.h's form) compiled as plain C++ into a program of its own with AddressSanitizer and UBSan (tests/recruit_read_main.cpp; run directly), over the withheld, the edge, the
     ins = del = 0 and the max_insert case: inside the program the kernel's form -- tiles, per-wave slots, two passes, the 16-lane band
     -- equals a sequential restatement in every output bit for bit; its output equals the numpy restatement."""
     exe = str(tmp_path / "recruit_read_main")
