@@ -28,17 +28,6 @@
 #ifndef FIG_EMU
 #define FIG_FI __device__ static __forceinline__
 
-// ---- wave maximum of a non-negative double through its bit pattern (positive doubles order like their 64-bit integers):
-// v_max_u32 with DPP row shifts / broadcasts on the high words, then on the low words of the lanes that hold the maximal
-// high word.  Result in every lane (hi, lo).
-FIG_D unsigned fig_wave_max_u32(unsigned v) {
-#define FIG_DPP_UMAX(ctrl, rmask) do { const unsigned y_ = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xf, false); v = y_ > v ? y_ : v; } while (0)
-    FIG_DPP_UMAX(0x111, 0xf); FIG_DPP_UMAX(0x112, 0xf); FIG_DPP_UMAX(0x114, 0xf); FIG_DPP_UMAX(0x118, 0xf);
-    FIG_DPP_UMAX(0x142, 0xa); FIG_DPP_UMAX(0x143, 0xc);
-#undef FIG_DPP_UMAX
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 // ---- log10 for the E-step weights (`fig_log10_fast` in DESIGN.md), ~40 FP64 operations against ~105 of the library's (which became a quarter of the E-step's
 // vector work once the chains cost 1.75 operations a step): x = m 2^e with m in [sqrt(1/2), sqrt(2)), s = (m-1)/(m+1) through
 // v_rcp_f64 + one Newton step with the quotient's rounding error recovered (s_lo), log m = 2 s + s z q(z) (atanh series in
@@ -225,21 +214,78 @@ FIG_FI void fig_sh_chain(double (&p)[FIG_SH_C], const FigPQ *colp, int ncolE, fi
     if (j < L) fig_sh_step<NS>(p, w0, k0, a0, w1, k1, a1, colp, ncolE, st, ktf, ktr, j + 1);
 }
 
-// One unit = (tile of 64 placements, NS reads [s0, s0 + NS) of the chunk): products start from the insert-size terms
-// (1.0 for a placement outside the read's window: never used), run the chain and go to the workgroup's product rows in the
-// scratch slab, prow[s * pst + (o + L - 1)] (coalesced 512-byte stores; read back four reads at a time by phase B).
-// Lanes past the last placement (vo false) run on the tile's first placement and store nothing.
+// ---- the per-read maxima of a unit: NS products per lane (lanes = placements) -> for every read the maximum over the wave's
+// 64 lanes, by a transposing reduction.  A fold takes the values of two reads, hands each lane's copy of one of them to a
+// partner lane and keeps the larger of its own and the partner's copy of the other: half the values per lane, each the
+// maximum over twice the lanes, and no chain of cross-lane steps per read.  The first two folds pair lane l with l ^ 32 and
+// l ^ 16 through v_permlane32_swap / v_permlane16_swap (two swaps and a maximum per pair of reads), the later ones through
+// DPP inside a row of 16 lanes (l ^ 8 as row_ror:8, l <-> 7 - l inside 8 lanes, l ^ 2 and l ^ 1 as quad permutations: two
+// selects per side, two moves, a maximum).  After log2 NS folds lane l holds read l >> (6 - log2 NS); what is left of the lane
+// index is reduced with the same DPP moves.  Products are non-negative and never NaN, so v_max_f64 orders them like their bit
+// patterns (written as an instruction: fmax() canonicalises its operands first).
+typedef unsigned long long __attribute__((address_space(1))) *fig_gu64p;
+typedef int __attribute__((address_space(1))) *fig_gi32p;
+FIG_FI double fig_sh_vmax(double a, double b) { double m; asm("v_max_f64 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b)); return m; }
+template <bool ROW32> FIG_FI double fig_sh_fold_swap(double a, double b) {
+    unsigned long long ab, bb; memcpy(&ab, &a, 8); memcpy(&bb, &b, 8);
+    const unsigned al = (unsigned)ab, ah = (unsigned)(ab >> 32), bl = (unsigned)bb, bh = (unsigned)(bb >> 32);
+    const auto l = ROW32 ? __builtin_amdgcn_permlane32_swap(al, bl, false, false) : __builtin_amdgcn_permlane16_swap(al, bl, false, false);
+    const auto h = ROW32 ? __builtin_amdgcn_permlane32_swap(ah, bh, false, false) : __builtin_amdgcn_permlane16_swap(ah, bh, false, false);
+    ab = ((unsigned long long)h[0] << 32) | l[0]; bb = ((unsigned long long)h[1] << 32) | l[1];
+    memcpy(&a, &ab, 8); memcpy(&b, &bb, 8);
+    return fig_sh_vmax(a, b);
+}
+template <int CTRL> FIG_FI double fig_sh_dpp(double v) {
+    unsigned long long b; memcpy(&b, &v, 8);
+    const unsigned l = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xf, 0xf, false);
+    const unsigned h = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, false);
+    b = ((unsigned long long)h << 32) | l; memcpy(&v, &b, 8);
+    return v;
+}
+template <int CTRL> FIG_FI double fig_sh_fold_dpp(double x, double y, bool up) { return fig_sh_vmax(up ? y : x, fig_sh_dpp<CTRL>(up ? x : y)); }
+#define FIG_SH_DPP_X8 0x128          // row_ror:8
+#define FIG_SH_DPP_M8 0x141          // row_half_mirror
+#define FIG_SH_DPP_X2 0x4e           // quad_perm:[2,3,0,1]
+#define FIG_SH_DPP_X1 0xb1           // quad_perm:[1,0,3,2]
 template <int NS>
-FIG_FI void fig_sh_unit(const int s0, FigState &S, const FigHotU &U, const FigPQ *PQ, fig_cu32p stream, fig_gdp prow, const int pst, const int o, const bool vo, const int ocalc) {
+FIG_FI double fig_sh_readmax(double (&q)[FIG_SH_C], const int lane) {
+#pragma unroll
+    for (int j = 0; j < NS / 2; j++) q[j] = fig_sh_fold_swap<true>(q[j], q[j + NS / 2]);
+#pragma unroll
+    for (int j = 0; j < NS / 4; j++) q[j] = fig_sh_fold_swap<false>(q[j], q[j + NS / 4]);
+    if (NS >= 8) {
+#pragma unroll
+        for (int j = 0; j < NS / 8; j++) q[j] = fig_sh_fold_dpp<FIG_SH_DPP_X8>(q[j], q[j + NS / 8], (lane & 8) != 0);
+    } else q[0] = fig_sh_vmax(q[0], fig_sh_dpp<FIG_SH_DPP_X8>(q[0]));
+    if (NS >= 16) {
+#pragma unroll
+        for (int j = 0; j < NS / 16; j++) q[j] = fig_sh_fold_dpp<FIG_SH_DPP_M8>(q[j], q[j + NS / 16], (lane & 4) != 0);
+    } else q[0] = fig_sh_vmax(q[0], fig_sh_dpp<FIG_SH_DPP_M8>(q[0]));
+    if (NS >= 32) q[0] = fig_sh_fold_dpp<FIG_SH_DPP_X2>(q[0], q[1], (lane & 2) != 0);
+    else q[0] = fig_sh_vmax(q[0], fig_sh_dpp<FIG_SH_DPP_X2>(q[0]));
+    return fig_sh_vmax(q[0], fig_sh_dpp<FIG_SH_DPP_X1>(q[0]));
+}
+
+// One unit = (tile of 64 placements, NS reads [s0, s0 + NS) of the chunk): products start from the insert-size terms, run
+// the chain and go to the workgroup's product rows in the scratch slab, prow[s * pst + (o + L - 1)] (coalesced 512-byte
+// stores; read back four reads at a time by phase B).  A product that is no placement of a regular read starts from 0.0
+// and stays 0.0: a placement outside the read's window, a lane past the last placement (vo false: it runs on the tile's
+// first placement and stores nothing), a slot whose read takes the generic chain or lies past the last read (their
+// stream entries multiply by 1.0).  So the maximum over all lanes is the read's maximal product of this tile; it goes to
+// mxw[s] (the read's maxlv word) by an atomic maximum on the bit pattern, which executes in L2.
+template <int NS>
+FIG_FI void fig_sh_unit(const int s0, FigState &S, const FigHotU &U, const FigPQ *PQ, fig_cu32p stream, fig_gdp prow, const int pst, const int o, const bool vo, const int ocalc,
+                        const fig_gu64p mxw, const int nrd, const int lane, unsigned long long &epi) {
     // s0 = first read of the unit, counted from the super-chunk's first read (S.sh_* / prow row index); `stream` = its chunk's rows
     const fig_lsp SL = (fig_lsp)&S;
     double p[FIG_SH_C];
 #pragma unroll
     for (int i = 0; i < NS; i++) {
         const int s = s0 + i;
-        const int lo = fig_u(SL->sh_lo[s]), hi = fig_u(SL->sh_hi[s]), tis0 = fig_u(SL->sh_tis0[s]), dir = (fig_u(SL->sh_aux[s]) & 4) ? 1 : -1;
-        p[i] = 1.0;
-        if (ocalc >= lo && ocalc <= hi) p[i] = ((fig_gcdp)U.insd)[tis0 + dir * ocalc];
+        const int lo = fig_u(SL->sh_lo[s]), tis0 = fig_u(SL->sh_tis0[s]), dir = (fig_u(SL->sh_aux[s]) & 4) ? 1 : -1;
+        const int hi = ((fig_u((int)SL->sh_irr[s >> 5]) >> (s & 31)) & 1) ? -0x8000 : fig_u(SL->sh_hi[s]);
+        p[i] = 0.0;
+        if (vo && ocalc >= lo && ocalc <= hi) p[i] = ((fig_gcdp)U.insd)[tis0 + dir * ocalc];
     }
     fig_sh_chain<NS>(p, PQ + (ocalc + U.xoff), U.ncolE, stream + ((s0 & (FIG_SH_C - 1)) >> 1), (fig_cdp)U.kt_fwd, (fig_cdp)U.kt_rev, U.L);
     if (vo) {
@@ -247,6 +293,29 @@ FIG_FI void fig_sh_unit(const int s0, FigState &S, const FigHotU &U, const FigPQ
 #pragma unroll
         for (int i = 0; i < NS; i++) dst[(long long)i * pst] = p[i];
     }
+#ifdef FIG_PROF
+    const unsigned long long t0 = __builtin_readcyclecounter();
+#endif
+    constexpr int SH = NS == 32 ? 1 : NS == 16 ? 2 : NS == 8 ? 3 : 4;          // lanes per read after the folds: 1 << SH
+    const double m = fig_sh_readmax<NS>(p, lane);
+    unsigned long long mb; memcpy(&mb, &m, 8);
+    const int s = s0 + (lane >> SH);
+    if ((lane & ((1 << SH) - 1)) == 0 && mb != 0ULL && s < nrd) __hip_atomic_fetch_max(mxw + s, mb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef FIG_PROF
+    epi += __builtin_readcyclecounter() - t0;
+#else
+    (void)epi;
+#endif
+}
+
+// The algorithmic flops of a regular read's placements, as the reference counts them: 4 L + fig_ovl(o, L, G) for every offset
+// o of the window [lo, hi] inside [-(L-1), G-1].  There fig_ovl = min(o + L, G) - max(o, 0) > 0, and both terms sum in closed form.
+FIG_FI unsigned long long fig_sh_credit(int lo, int hi, int L, int G) {
+    const long long a = lo > -(L - 1) ? lo : -(L - 1), b = hi < G - 1 ? hi : G - 1;
+    if (b < a) return 0;
+    const auto upto = [](long long n) { return n > 0 ? n * (n + 1) / 2 : 0LL; };                              // sum of max(o, 0) for o <= n
+    const auto capped = [&](long long n) { return n <= G ? n * (n + 1) / 2 : (long long)G * (G + 1) / 2 + (n - G) * G; };   // sum of min(u, G) for 1 <= u <= n
+    return (unsigned long long)(4LL * L * (b - a + 1) + (capped(b + L) - capped(a + L - 1)) - (upto(b) - upto(a - 1)));
 }
 
 // ---- the E-step with the shared-factor placement phase.  Same contract as fig_hot_estep<LDS = true, CPL, TILED = false>.
@@ -298,8 +367,15 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
             }
             SL->sh_lo[tid] = (short)lo; SL->sh_hi[tid] = (short)hi; SL->sh_tis0[tid] = tis0; SL->sh_len[tid] = (unsigned char)len;
             SL->sh_aux[tid] = (unsigned char)((aux & 3) | (dir > 0 ? 4 : 0)); SL->sh_woff[tid] = (unsigned)(woff - wbase);
+            if (tid < nrd) {
+                // the read's maximal product collects in its maxlv word (phase A), its offset in hint_e (phase B); the flop
+                // credit of a regular read's placements depends on its window alone
+                E.scr.maxlv[r] = 0; E.scr.hint_e[r] = FIG_NOPOS;
+                if (!irr) fl_acc += fig_sh_credit(lo, hi, U.L, G);
+            }
             const unsigned long long im = fig_ballot(irr);
             if (lane == 0) { SL->sh_irr[2 * wave] = (unsigned)(im & 0xffffffffULL); SL->sh_irr[2 * wave + 1] = (unsigned)(im >> 32); }
+            __builtin_amdgcn_s_waitcnt(0x0f70);                // vmcnt(0): the cleared words are in L2 before any wave's atomics follow
         }
         FIG_SYNC();
         // position lists of the first row group: fetched now, parked in plb when the group starts (wave t: row t)
@@ -310,9 +386,13 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
             if (lane < ndw) plv_next = ((fig_gcu32p)U.packed)[wbase + fig_u((int)SL->sh_woff[wave]) + ((len + 15) >> 4) + ((len + 31) >> 5) + lane];
         }
         FIG_TICK(E, 34);
-        // ---- phase A: lanes = placements, the raw products of all reads -> prow.  Work items = (chunk, tile) pairs: full
-        // rounds of nw items with all 32 reads of their chunk; the items left over are split by reads over f waves each.
+        // ---- phase A: lanes = placements, the raw products of all reads -> prow, the per-read maxima -> maxlv.  Work items =
+        // (chunk, tile) pairs: full rounds of nw items with all 32 reads of their chunk; the items left over are split by reads
+        // over f waves each.
+        const fig_gu64p mxw = (fig_gu64p)fig_uptr(E.scr.maxlv) + c0;      // the super-chunk's maxlv words as bit patterns
+        const fig_gi32p hnw = (fig_gi32p)fig_uptr(E.scr.hint_e) + c0;
         {
+            unsigned long long epi = 0;                        // FIG_PROF: cycles in the units' maxima epilogues (a part of slot 35)
             const int nit = nT * nc;
             const int nfull = nit / nw, mleft = nit - nfull * nw;
             const fig_cu32p stc = stream0 + (long long)(c0 / FIG_SH_C) * U.L * (FIG_SH_C / 2);
@@ -320,7 +400,7 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
                 const int it = k * nw + wave, ci = it / nT, tl = it - ci * nT;
                 const int ob = -(U.L - 1) + 64 * tl, o = ob + lane;
                 const bool vo = o <= G - 1;
-                fig_sh_unit<32>(ci * FIG_SH_C, S, U, PQ, stc + (long long)ci * U.L * (FIG_SH_C / 2), prow, pst, o, vo, vo ? o : ob);
+                fig_sh_unit<32>(ci * FIG_SH_C, S, U, PQ, stc + (long long)ci * U.L * (FIG_SH_C / 2), prow, pst, o, vo, vo ? o : ob, mxw, nrd, lane, epi);
             }
             if (mleft > 0) {
                 int fsplit = 1;
@@ -332,15 +412,18 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
                     const int ob = -(U.L - 1) + 64 * tl, o = ob + lane;
                     const bool vo = o <= G - 1;
                     const fig_cu32p stp = stc + (long long)ci * U.L * (FIG_SH_C / 2);
-                    if (fsplit == 1) fig_sh_unit<32>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob);
-                    else if (fsplit == 2) fig_sh_unit<16>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob);
-                    else if (fsplit == 4) fig_sh_unit<8>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob);
-                    else fig_sh_unit<4>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob);
+                    if (fsplit == 1) fig_sh_unit<32>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob, mxw, nrd, lane, epi);
+                    else if (fsplit == 2) fig_sh_unit<16>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob, mxw, nrd, lane, epi);
+                    else if (fsplit == 4) fig_sh_unit<8>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob, mxw, nrd, lane, epi);
+                    else fig_sh_unit<4>(s0, S, U, PQ, stp, prow, pst, o, vo, vo ? o : ob, mxw, nrd, lane, epi);
                 }
             }
+            FIG_COUNT(E, 25, epi);
+            // the maxima are atomics without a return value: they have executed in L2 before this wave passes the barrier
+            __builtin_amdgcn_s_waitcnt(0x0f70);                // vmcnt(0), lgkmcnt / expcnt untouched
         }
         FIG_TICK(E, 35);
-        FIG_SYNC();                                            // every wave's products are in prow
+        FIG_SYNC();                                            // every wave's products are in prow, every read's maximum in maxlv
         // ---- phase B: four reads at a time through the LDS weight rows.  Thread tid takes placements tid, tid + nt, ... of
         // every row; the products of the next group are fetched while this group's column pass runs.
         double pn[NR][KP];
@@ -348,6 +431,11 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
         for (int t = 0; t < NR; t++)
 #pragma unroll
             for (int k = 0; k < KP; k++) { const int i = tid + k * U.nt; pn[t][k] = (i < Wn && c0 + t < nU) ? prow[(long long)t * pst + i] : 0.0; }
+        // the rows' maxima travel with their products.  The words were written by atomics in L2, past this CU's vector cache:
+        // an atomic load of agent scope goes to L2 as well (a plain load may hit a line from before the atomics)
+        unsigned long long mn[NR];
+#pragma unroll
+        for (int t = 0; t < NR; t++) mn[t] = t < nrd ? __hip_atomic_load(mxw + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL;
         for (int q0 = 0; q0 < nrd; q0 += NR) {
             const unsigned irr = (unsigned)fig_u((int)SL->sh_irr[q0 >> 5]) >> (q0 & 31);      // bits 0..NR-1: the group's reads
             // the group's scalars, all four rows at once (lane t of every wave reads row t's, v_readlane hands them round)
@@ -368,6 +456,9 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
             for (int t = 0; t < NR; t++)
 #pragma unroll
                 for (int k = 0; k < KP; k++) pc[t][k] = pn[t][k];
+            double mc[NR];
+#pragma unroll
+            for (int t = 0; t < NR; t++) memcpy(&mc[t], &mn[t], 8);
             FIG_TICK(E, 19);
             // w = exp(0.5 log10 p) of the group's four rows side by side: four independent dependent chains in one basic block,
             // which the scheduler interleaves (a row's own ~90-operation chain alone leaves the FP64 pipe half empty at two
@@ -396,37 +487,23 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
                 const bool isirr = (irr >> t) & 1u;
                 if (hi < lo) continue;
                 if (!isirr) {
-                    // weights of this read's placements: w = exp(0.5 log10 p) inside the read's window, 0 outside (:3591-3601);
-                    // the wave's maximal product (a non-negative double orders like its bit pattern) and one offset that
-                    // reaches it go to wv_v / wv_o
-                    double pr = 0.0; int po = FIG_NOPOS;
+                    // weights of this read's placements: w = exp(0.5 log10 p) inside the read's window, 0 outside (:3591-3601).
+                    // The read's maximal product is known from phase A (mc[t]; 0 is no placement: log10 = -inf never beats
+                    // -DBL_MAX); its offset is the "first maximum" rule over the products at hand: in a wave the lowest lane
+                    // that holds the maximum and that lane's smallest k, over the waves the smallest such offset.
+                    int po = FIG_NOPOS;
 #pragma unroll
-                    for (int k = 0; k < KP; k++) {
+                    for (int k = KP - 1; k >= 0; k--) {
                         const int i = tid + k * U.nt, o = i - (U.L - 1);
                         if (k * U.nt + wave * 64 < Wn) {        // (wave-uniform: a wave without placements in this pass skips it)
                             const bool in = i < Wn && o >= lo && o <= hi;
                             if (i < Wn) wrow[o] = in ? wq[t][k] : 0.0;
-                            if (in) {
-                                fl_acc += 4ULL * (unsigned long long)U.L + (unsigned long long)fig_ovl(o, U.L, G);
-                                if (pc[t][k] > pr) { pr = pc[t][k]; po = o; }
-                            }
+                            if (in && pc[t][k] == mc[t]) po = o;
                         }
                     }
                     FIG_TICK(E, 20);
-                    long long bits; memcpy(&bits, &pr, 8);
-                    const unsigned hi32 = (unsigned)((unsigned long long)bits >> 32), lo32 = (unsigned)((unsigned long long)bits & 0xffffffffULL);
-                    const unsigned mh = fig_wave_max_u32(hi32);
-                    const unsigned long long ah = fig_ballot(hi32 == mh);
-                    // (nearly always one lane holds the maximal high word: its low word is the maximum's)
-                    const unsigned ml = (ah & (ah - 1)) == 0ULL ? (unsigned)fig_lane_read_i32((int)lo32, fig_ctz64(ah)) : fig_wave_max_u32(hi32 == mh ? lo32 : 0u);
-                    const unsigned long long am = fig_ballot(po != FIG_NOPOS && hi32 == mh && lo32 == ml);
-                    const bool any = (mh | ml) != 0u && am != 0ULL;            // a product of 0 is no placement: log10 = -inf never beats -DBL_MAX
-                    const int ao = any ? fig_lane_read_i32(po, fig_ctz64(am)) : FIG_NOPOS;
-                    if (lane == 0) {
-                        const unsigned long long mb = ((unsigned long long)mh << 32) | ml;
-                        double mv; memcpy(&mv, &mb, 8);
-                        SL->wv_v[t * 8 + wave] = any ? mv : 0.0; SL->wv_o[t * 8 + wave] = ao;
-                    }
+                    const unsigned long long am = fig_ballot(po != FIG_NOPOS && mc[t] > 0.0);
+                    if (am != 0ULL && lane == fig_ctz64(am)) __hip_atomic_fetch_min(hnw + s, po, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     FIG_TICK(E, 21);
                 } else {
                     // generic chain (N bases / short read): all lanes over the read's window, zero outside it
@@ -453,6 +530,7 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
                     if (lane == 0) { SL->wv_v[t * 8 + wave] = bv; SL->wv_o[t * 8 + wave] = bv > -FIG_DBL_MAX ? ao : FIG_NOPOS; }
                 }
             }
+            __builtin_amdgcn_s_waitcnt(0x0f70);                // vmcnt(0): a wave that sent an offset to hint_e has it in L2 behind the barrier
             FIG_TICK(E, 36);
             FIG_SYNC();
             FIG_TICK(E, 37);
@@ -462,15 +540,17 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
                 for (int t = 0; t < NR; t++)
 #pragma unroll
                     for (int k = 0; k < KP; k++) { const int i = tid + k * U.nt; pn[t][k] = (i < Wn && c0 + q0 + NR + t < nU) ? prow[(long long)(q0 + NR + t) * pst + i] : 0.0; }
+#pragma unroll
+                for (int t = 0; t < NR; t++) mn[t] = q0 + NR + t < nrd ? __hip_atomic_load(mxw + (q0 + NR + t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL;
             }
-            // ---- per-read bookkeeping (:3680-3688): regular reads hold products in wv_v (maxlv = log10 of the maximum: the
-            // same value the placement's own log10 gave), reads of the generic chain hold log10 values
-            if (tid >= 64 && tid < 64 + NR) {
+            // ---- per-read bookkeeping (:3680-3688) of the group's reads of the generic chain: wv_v holds log10 values, one per
+            // wave (a regular read's maximum and offset are in maxlv / hint_e already and are finished per super-chunk below)
+            if ((irr & ((1u << NR) - 1u)) != 0u && tid >= 64 && tid < 64 + NR) {
                 const int t = tid - 64, s = q0 + t;
-                if (c0 + s < nU) {
+                if (c0 + s < nU && ((irr >> t) & 1u)) {
                     FigBest b; b.v = -FIG_DBL_MAX; b.o = FIG_NOPOS;
                     if (SL->sh_hi[s] >= SL->sh_lo[s]) for (int k = 0; k < nw; k++) { FigBest y; y.v = SL->wv_v[t * 8 + k]; y.o = SL->wv_o[t * 8 + k]; b = fig_best_merge(b, y); }
-                    if (b.o != FIG_NOPOS) E.scr.maxlv[c0 + s] = b.v;   // (regular reads: the product; its log10 is taken per super-chunk below)
+                    if (b.o != FIG_NOPOS) E.scr.maxlv[c0 + s] = b.v;
                     else { E.scr.maxlv[c0 + s] = 0; fig_atomic_add_i32(&S.invalid_count, 1); }
                     E.scr.hint_e[c0 + s] = b.o;
                 }
@@ -560,10 +640,19 @@ FIG_NOINLINE FIG_D void fig_hot_estep_sh(FigEng &E, int gapoffset) {
             FIG_SYNC();
             FIG_TICK(E, 39);
         }
-        // maxlv of the super-chunk's regular reads: log10 of the maximal product, one read per thread
+        // maxlv of the super-chunk's regular reads: log10 of the maximal product, one read per thread (the same value the
+        // placement's own log10 gave).  A read without a placement or with products of 0 only ends as maxlv = 0, hint_e =
+        // FIG_NOPOS and one more invalid read.  Both words were last written by atomics in L2: they are read there and
+        // stored back, so that the plain loads of the passes behind the E-step find them in this CU's vector cache too.
         if (tid < nrd) {
             const bool isirr = (SL->sh_irr[tid >> 5] >> (tid & 31)) & 1u;
-            if (!isirr && E.scr.hint_e[c0 + tid] != FIG_NOPOS) E.scr.maxlv[c0 + tid] = fig_log10(E.scr.maxlv[c0 + tid]);
+            if (!isirr) {
+                const unsigned long long mb = __hip_atomic_load(mxw + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int ho = __hip_atomic_load(hnw + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                double mv; memcpy(&mv, &mb, 8);
+                if (mb != 0ULL) { E.scr.maxlv[c0 + tid] = fig_log10(mv); E.scr.hint_e[c0 + tid] = ho; }
+                else { E.scr.maxlv[c0 + tid] = 0; E.scr.hint_e[c0 + tid] = FIG_NOPOS; fig_atomic_add_i32(&S.invalid_count, 1); }
+            }
         }
     }
 #pragma unroll
